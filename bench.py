@@ -19,6 +19,9 @@ hipEvents on the launch stream by the library's measurement hook), `cpu_baseline
 restatement of the same path on a bounded sample, rank 0 / N=1 only) and `extra` (N=1: the same step in direct
 form without Winograd, and a step of multi-snippet 309-frame videos -- the reference's run_example shape: 5 snippets,
 GRU seq_len 5).
+
+`--dump-outputs DIR` writes the valence / arousal rows the last timed step returned (DIR/valence_arousal.npy, float32): inputs and
+weights are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes
@@ -31,11 +34,8 @@ import time
 T_PROCESS_START = time.time()
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# One hardware queue per HIP stream this process uses: the three lane streams, torch's default stream, the copy stream of a
-# streamed input and RCCL's own stream.  The runtime's default of 4 queues makes two of them share one as soon as the RCCL
-# process group exists, which serialises two lanes: measured 111.6 vs 107.5 ms per step with / without a (one-rank) RCCL group,
-# 108.2 vs 107.9 with 8 queues (tools/ab_force_dist.sh).  Read by the HIP runtime when it initialises: set before torch loads it.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+# The number of hardware queues the HIP runtime opens per process is left to the environment: the lane streams, torch's default
+# stream, the copy stream of a streamed input and RCCL's own stream share whatever queues the runtime provides.
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
@@ -399,6 +399,23 @@ def cpu_baseline(n_clips, resnet_sd):
                                    "%.1f s wall; per process: %s" % (wall3, stages(recs3))}}, cpu_out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, rows):
+    """--dump-outputs: the [frames, 2] valence / arousal rows the last timed step returned (rank-major at N > 1, NaN rows for the
+    empty slots of a ragged tail) as DIR/valence_arousal.npy, float32.  Rows that would pass the 64 MB budget are thinned to a fixed,
+    seeded sample, whose row indices go to DIR/valence_arousal_rows.npy (float64)."""
+    os.makedirs(dirname, exist_ok=True)
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    if rows.nbytes > DUMP_LIMIT_BYTES:
+        n_keep = (DUMP_LIMIT_BYTES - 4096) // (rows[0].nbytes + 8)          # (4 KB: the two .npy headers)
+        keep = np.sort(np.random.default_rng(0).choice(len(rows), n_keep, replace=False))
+        np.save(os.path.join(dirname, "valence_arousal_rows.npy"), keep.astype(np.float64))
+        rows = rows[keep]
+    np.save(os.path.join(dirname, "valence_arousal.npy"), rows)
+
+
 # ---------------------------------------------------------------------------------------------------------
 # compute back ends
 # ---------------------------------------------------------------------------------------------------------
@@ -582,6 +599,8 @@ def parse_args(argv=None):
                     help="diagnosis only: keep the process group but skip the per-step all-gather of the result rows")
     ap.add_argument("--stub-compute", action="store_true", help="testing only: no GPU work (launcher / work-queue plumbing)")
     ap.add_argument("--dump-out", default="", help="testing only: rank 0 saves the gathered rows of the last step (.npy)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the last timed step returned as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--no-winograd", action="store_true", help="run every 3x3 layer in the direct implicit-GEMM form")
     ap.add_argument("--winograd", type=int, default=1, help="1 = default (F(4x4,3x3); conv2_x..conv4_x with the output transform fused into the position GEMMs), 2 = F(2x2,3x3), 4 = F(4x4,3x3) as three kernels everywhere, 5 = fused everywhere")
     ap.add_argument("--lanes", type=int, default=3, help="HIP streams the clips of a step are spread over (1 = single stream)")
@@ -601,6 +620,8 @@ def main():
         _cpu_worker(int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), sys.argv[5], int(sys.argv[6]) if len(sys.argv) > 6 else 0)
         return 0
     args = parse_args()
+    if args.steps < 1 and not args.whole_job:
+        raise SystemExit("bench.py: --steps must be >= 1")
     if args.stream_input and args.from_f32:
         raise SystemExit("bench.py: --stream-input streams the uint8 boundary; it cannot be combined with --from-f32")
     import mimamo_net_amd  # noqa: F401
@@ -679,15 +700,24 @@ def run_rank(args):
     # The [frames,2] results of a step are all-gathered (8 B/frame, the only collective besides the queue broadcast).  It
     # is issued asynchronously on RCCL's stream and only waited for one step later, so a rank never stalls on a slower
     # peer inside a step -- ranks are independent shards and the job time is the slowest rank's, not a sum of maxima.
-    pending = []
+    # A step's gather is issued once the NEXT step's kernels are enqueued: RCCL's stream may share a hardware queue with a
+    # lane, and its wait for the step's rows must then sit behind that lane's next work, not in front of it.
+    pending = []      # issued gathers: (handle, buffers, rows)
+    ready = []        # rows of the latest step, gather not issued yet
     last = {}
 
     def drain():
         while pending:
-            h, bufs, keep = pending.pop()
+            h, bufs, keep = pending.pop(0)
             if h is not None:
                 h.wait()
             last["gathered"] = bufs
+
+    def issue():
+        while ready:
+            out_g = ready.pop()
+            h, bufs = mdist.all_gather_rows_async(out_g, world)
+            pending.append((h, bufs, out_g))
 
     def step(ids, nxt=None):
         if not ids:
@@ -705,13 +735,14 @@ def run_rank(args):
                 out_g = pad
             else:
                 out_g = out
-            h, bufs = mdist.all_gather_rows_async(out_g, world)
-            pending.append((h, bufs, out_g))
+            issue()
+            ready.append(out_g)
         else:
             last["gathered"] = [out]
         return out
 
     def fence():
+        issue()
         drain()
         mdist.barrier()
         comp.sync()
@@ -737,6 +768,8 @@ def run_rank(args):
         assert torch.isfinite(out).all()
     if args.dump_out and rank == 0:
         np.save(args.dump_out, torch.cat([t.cpu() for t in last["gathered"]], 0).numpy())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, torch.cat([t.cpu() for t in last["gathered"]], 0).numpy())
 
     n_frames = per_step * FRAMES_PER_CLIP
     result = {

@@ -41,8 +41,9 @@ def init(backend=None, device_index=None, force=False):
             backend = "nccl" if torch.cuda.is_available() else "gloo"
         kw = {}
         # bind a GPU only where one is asked for: RCCL ranks (one per GPU), or an explicit device_index.  A gloo plumbing run
-        # on a GPU host with fewer GPUs than ranks (tests, --stub-compute) must not touch cuda:<local_rank>
-        if torch.cuda.is_available() and (backend == "nccl" or device_index is not None):
+        # on a GPU host with fewer GPUs than ranks (tests, --stub-compute) must not touch cuda:<local_rank>, nor open the GPU at all
+        # (asking the runtime whether a device exists already does)
+        if (backend == "nccl" or device_index is not None) and torch.cuda.is_available():
             torch.cuda.set_device(local_rank if device_index is None else device_index)
             if backend == "nccl":
                 kw["device_id"] = torch.device("cuda", torch.cuda.current_device())
@@ -284,9 +285,7 @@ def spawn_ranks(argv, n_ranks, env=None, timeout=None):
     import time
     base = dict(os.environ if env is None else env)
     base.update({"WORLD_SIZE": str(n_ranks), "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(free_port()),
-                 "HSA_ENABLE_IPC_MODE_LEGACY": base.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"),
-                 # a hardware queue per stream (lanes + default + copy + RCCL's): see bench.py
-                 "GPU_MAX_HW_QUEUES": base.get("GPU_MAX_HW_QUEUES", "8")})
+                 "HSA_ENABLE_IPC_MODE_LEGACY": base.get("HSA_ENABLE_IPC_MODE_LEGACY", "0")})
     tmp = tempfile.mkdtemp(prefix="mm_ranks_")
     procs, files = [], []
     for r in range(n_ranks):

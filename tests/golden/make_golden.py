@@ -11,6 +11,7 @@ arguments and the reference's outputs are saved.
   G2 pyramid.npz    build_pyramid of 4 textured 48x48 frames: fp32 and fp64 reference, + the
                     independent SCFpyr_NumPy result for frame 0
   G3 extract.npz    Tester.phase_diff_output on 3 windows (moving / edge-clamped / fast-moving)
+  G3c extract_cbwr_compatible.npz  the same on MKL's generic code path (MKL_CBWR=COMPATIBLE), the path MKL takes on some x86 hosts
   KAT kats.npz      torch_unwrap, torch_diff, gaussian_kernel, symmetric_extension_batch, blur
   G4 head.npz       Two_Stream_RNN(eval) with generated weights, bs in {1,3}, T=4
   G8 scfpyr_full.npz  SCFpyr_PyTorch.build (the FULL list: hi-pass residual, every band, low-pass residual) on
@@ -130,6 +131,17 @@ def g3_extract(ref):
                         phase_0_f64=q0.numpy()[0].astype(np.float32), phase_1_f64=q1.numpy()[0].astype(np.float32))
     d0 = np.abs(p0.numpy() - q0.numpy())
     print("G3", p0.shape, p1.shape, "fp32-vs-fp64 max", d0.max(), "p99.99", np.quantile(d0, 0.9999))
+
+
+def g3c_extract_compatible(ref):
+    """G3 on MKL's generic code path: MKL picks its FFT kernels by CPU, and on these windows the fp32 outputs of the path it takes on one
+    x86 host and of the generic path differ by up to 3e-5.  Run as `MKL_CBWR=COMPATIBLE python make_golden.py g3c` (read when MKL loads)."""
+    assert os.environ.get("MKL_CBWR") == "COMPATIBLE", "run with MKL_CBWR=COMPATIBLE in the environment"
+    pde = ref.Phase_Difference_Extractor(4, 2, 2, [1, 2], False)
+    torch.set_default_dtype(torch.float32)
+    p0, p1 = ref.Tester.phase_diff_output(None, torch.from_numpy(make_windows()), pde)
+    np.savez_compressed(os.path.join(HERE, "extract_cbwr_compatible.npz"), phase_0=p0.numpy()[0], phase_1=p1.numpy()[0])
+    print("G3c", p0.shape, p1.shape)
 
 
 def kats(ref):
@@ -488,6 +500,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if sys.argv[1:] == ["g9"]:
         g9_phase_generic(ref)
+        sys.exit(0)
+    if sys.argv[1:] == ["g3c"]:
+        g3c_extract_compatible(ref)
         sys.exit(0)
     if sys.argv[1:] == ["g8"]:
         g8_scfpyr_full(ref)

@@ -36,30 +36,44 @@ def test_two_ranks_compute_the_same_rows_as_one(tmp_path):
         np.testing.assert_array_equal(two[pos * 64:(pos + 1) * 64], one[clip * 64:(clip + 1) * 64])
 
 
-def test_eight_ranks_on_one_device_whole_job_with_a_ragged_tail(tmp_path):
-    """The shape of the driver's 8-GPU run on the one GPU of the test box: 8 gloo ranks sharing cuda:0 on REAL compute, the whole
-    13-clip queue walked once (ranks 0-4 hold two clips, ranks 5-7 one: their second step is NaN-padded), the clip pool generated
-    once across the job and all-gathered, eight per-rank rows.  Gathered rows of the last step equal the single-rank run."""
-    common = ("--whole-job", "--total-clips", 13, "--distinct-clips", 13, "--warmup", 1, "--no-cpu-baseline", "--no-extra", "--lanes", 1)
-    d8 = _bench("--gpus", 8, "--same-device", "--backend", "gloo", "--clips", 1, "--dump-out", tmp_path / "eight.npy", *common, timeout=1500)
-    d1 = _bench("--gpus", 1, "--clips", 13, "--dump-out", tmp_path / "one.npy", *common)
-    assert d8["n_gpus"] == 8 and d8["steps"] == 2 and d8["scaling"] == "strong" and d1["steps"] == 1
-    pr = d8["per_rank"]
-    assert [x["rank"] for x in pr] == list(range(8)) and all(x["device"] == 0 for x in pr)
-    assert [x["frames"] for x in pr] == [128] * 5 + [64] * 3
-    # 13 contents over 8 ranks: ceil = 2 per rank -> ranks 0-5 generate 2, rank 6 one, rank 7 none; nothing twice
-    assert [x["clip_contents_generated"] for x in pr] == [2, 2, 2, 2, 2, 2, 1, 0]
+def test_four_ranks_on_one_device_whole_job_with_a_ragged_tail(tmp_path):
+    """The shape of the driver's multi-GPU run on the one GPU of the test box: 4 gloo ranks sharing cuda:0 on REAL compute (with the
+    test process, no more than five processes hold the GPU), the whole 6-clip queue walked once (ranks 0-1 hold two clips, ranks 2-3
+    one: their second step is NaN-padded), the clip pool generated once across the job and all-gathered, four per-rank rows.
+    Gathered rows of the last step equal the single-rank run."""
+    common = ("--whole-job", "--total-clips", 6, "--distinct-clips", 6, "--warmup", 1, "--no-cpu-baseline", "--no-extra", "--lanes", 1)
+    d4 = _bench("--gpus", 4, "--same-device", "--backend", "gloo", "--clips", 1, "--dump-out", tmp_path / "four.npy", *common, timeout=1500)
+    d1 = _bench("--gpus", 1, "--clips", 6, "--dump-out", tmp_path / "one.npy", *common)
+    assert d4["n_gpus"] == 4 and d4["steps"] == 2 and d4["scaling"] == "strong" and d1["steps"] == 1
+    pr = d4["per_rank"]
+    assert [x["rank"] for x in pr] == list(range(4)) and all(x["device"] == 0 for x in pr)
+    assert [x["frames"] for x in pr] == [128] * 2 + [64] * 2
+    # 6 contents over 4 ranks: ceil = 2 per rank -> ranks 0-2 generate 2, rank 3 none; nothing twice
+    assert [x["clip_contents_generated"] for x in pr] == [2, 2, 2, 0]
     assert all(x["startup_s"] > 0 and x["cpus"] >= 1 for x in pr)
-    print("8 ranks on one device: startup %.1f-%.1f s, cpus per rank %s, bound %s" % (
+    print("4 ranks on one device: startup %.1f-%.1f s, cpus per rank %s, bound %s" % (
         min(x["startup_s"] for x in pr), max(x["startup_s"] for x in pr), sorted({x["cpus"] for x in pr}), sorted({x["numa_node"] is not None for x in pr})))
-    eight, one = np.load(tmp_path / "eight.npy"), np.load(tmp_path / "one.npy")
-    assert eight.shape == (8 * 64, 2) and one.shape == (13 * 64, 2) and np.isfinite(one).all()
-    for r in range(8):                       # last step: rank r's second clip is clip 8 + r (c mod 8 == r), ranks 5-7 have none
-        rows = eight[r * 64:(r + 1) * 64]
-        if r < 5:
-            np.testing.assert_array_equal(rows, one[(8 + r) * 64:(9 + r) * 64])
+    four, one = np.load(tmp_path / "four.npy"), np.load(tmp_path / "one.npy")
+    assert four.shape == (4 * 64, 2) and one.shape == (6 * 64, 2) and np.isfinite(one).all()
+    for r in range(4):                       # last step: rank r's second clip is clip 4 + r (c mod 4 == r), ranks 2-3 have none
+        rows = four[r * 64:(r + 1) * 64]
+        if r < 2:
+            np.testing.assert_array_equal(rows, one[(4 + r) * 64:(5 + r) * 64])
         else:
             assert np.isnan(rows).all()
+
+
+def test_dump_outputs_are_the_last_timed_step_and_repeat_bit_for_bit(tmp_path):
+    """`--dump-outputs DIR` on real compute: the rows of the last timed step (the same rows `--dump-out` saves), and with the same
+    arguments the same inputs and so the same bits in a second process."""
+    common = ("--steps", 3, "--warmup", 1, "--clips", 4, "--total-clips", 8, "--distinct-clips", 8, "--no-cpu-baseline", "--no-extra")
+    a = _bench("--dump-outputs", tmp_path / "a", "--dump-out", tmp_path / "rows.npy", *common)
+    b = _bench("--dump-outputs", tmp_path / "b", *common)
+    assert a["steps"] == b["steps"] == 3 and a["ms_per_step"] > 0
+    va, vb = np.load(tmp_path / "a" / "valence_arousal.npy"), np.load(tmp_path / "b" / "valence_arousal.npy")
+    assert va.dtype == np.float32 and va.shape == (4 * 64, 2) and np.isfinite(va).all()
+    np.testing.assert_array_equal(va, np.load(tmp_path / "rows.npy"))
+    np.testing.assert_array_equal(va, vb)
 
 
 def test_one_rank_process_group_over_rccl():
@@ -76,7 +90,7 @@ def test_forced_process_group_agrees_with_the_plain_single_rank_run():
     b = _bench("--force-dist", *common)
     assert "per_rank" not in a and len(b["per_rank"]) == 1 and b["per_rank"][0]["frames"] == 8 * 32 * 64
     assert b["per_rank"][0]["ms_per_step_local"] <= b["per_rank"][0]["ms_per_step"] * 1.001
-    # Round 3 found the RCCL group costing 4 % here: its stream took the hardware queue of a lane (GPU_MAX_HW_QUEUES, bench.py).
+    # Round 3 found the RCCL group costing 4 % here: its stream took the hardware queue of a lane.
     # Fresh processes of ONE mode differ by up to ~1 % (clocks, allocator state): each mode runs twice, interleaved, the better run
     # of each is compared, and the assert allows 2 %.
     a2 = _bench(*common)

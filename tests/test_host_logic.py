@@ -194,6 +194,34 @@ def test_bench_gpus_flag_must_match_launcher_world_size():
     assert r.returncode != 0 and d is None and "does not match WORLD_SIZE" in r.stderr
 
 
+def test_bench_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """`--dump-outputs DIR`: the rows the last of the `--steps` timed steps returned, float32, as DIR/valence_arousal.npy."""
+    out = tmp_path / "out"
+    r, d = _run_bench("--stub-compute", "--steps", 3, "--warmup", 1, "--clips", 2, "--total-clips", 10, "--distinct-clips", 10,
+                      "--dump-outputs", out)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert d["steps"] == 3 and d["ms_per_step"] >= 0
+    assert sorted(os.listdir(out)) == ["valence_arousal.npy"]
+    rows = np.load(out / "valence_arousal.npy")
+    # one warm-up + 3 timed steps of 2 clips: the last takes queue positions 6, 7
+    assert rows.dtype == np.float32 and rows.shape == (2 * 64, 2) and list(rows[::64, 0]) == [6, 7]
+    r, d = _run_bench("--stub-compute", "--steps", 0, "--dump-outputs", out)
+    assert r.returncode != 0 and d is None and "--steps" in r.stderr
+
+
+def test_bench_dump_outputs_samples_rows_over_the_budget(tmp_path, monkeypatch):
+    bench = _bench()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096 + 16 * 100)
+    rows = np.arange(1000 * 2, dtype=np.float32).reshape(1000, 2)
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), rows)
+    got, idx = np.load(tmp_path / "a" / "valence_arousal.npy"), np.load(tmp_path / "a" / "valence_arousal_rows.npy")
+    assert got.dtype == np.float32 and idx.dtype == np.float64 and got.shape == (100, 2) and (np.diff(idx) > 0).all()
+    np.testing.assert_array_equal(got, rows[idx.astype(np.int64)])
+    np.testing.assert_array_equal(got, np.load(tmp_path / "b" / "valence_arousal.npy"))      # the same sample every time
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= bench.DUMP_LIMIT_BYTES
+
+
 def test_bench_whole_job_walks_the_queue_once_with_a_ragged_tail(tmp_path):
     dump = str(tmp_path / "rows.npy")
     r, d = _run_bench("--gpus", 3, "--stub-compute", "--whole-job", "--total-clips", 11, "--clips", 2, "--distinct-clips", 11,

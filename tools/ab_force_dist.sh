@@ -15,7 +15,5 @@ for i in $(seq 1 $R); do
   run "force-dist lanes=1" $B --force-dist --lanes 1
   run "plain lanes=1" $B --lanes 1
   run "force-dist TORCH_NCCL_ASYNC_ERROR_HANDLING=0" env TORCH_NCCL_ASYNC_ERROR_HANDLING=0 TORCH_NCCL_ENABLE_MONITORING=0 $B --force-dist
-  run "force-dist GPU_MAX_HW_QUEUES=8" env GPU_MAX_HW_QUEUES=8 $B --force-dist
-  run "plain GPU_MAX_HW_QUEUES=8" env GPU_MAX_HW_QUEUES=8 $B
   run "force-dist NCCL_MAX_NCHANNELS=1" env NCCL_MAX_NCHANNELS=1 NCCL_MIN_NCHANNELS=1 $B --force-dist
 done

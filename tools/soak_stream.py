@@ -2,7 +2,6 @@
 double buffer, alternating between several step contents; every step must give the bits of the same content computed from HBM-resident
 frames (a slot re-filled before its readers finished, or read before its upload landed, shows up as a mismatch)."""
 import os, sys
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
