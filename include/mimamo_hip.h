@@ -151,6 +151,8 @@ int mm_phase_diff_planes(mm_pyramid_t* h, const float* planes, int64_t n, const 
  * image: completeness, not speed), height >= 2, 2 <= nbands <= 16; otherwise MM_ERR_UNSUPPORTED;
  * `height > floor(log2(size)) - 2` returns MM_ERR_TOO_SMALL (the reference's RuntimeError, :90-91).
  * The inference hot path does not go through here (mm_pyramid_* exploits the mirrored input).
+ * mm_scfpyr_reconstruct is the inverse, `SCFpyr_PyTorch.reconstruct(coeff)` (:214-318), with the same limits; it and
+ * mm_scfpyr_host_recon_table were added without an MM_VERSION change (backward compatible, still 106).
  * ------------------------------------------------------------------------------------- */
 typedef struct mm_scfpyr mm_scfpyr_t;
 int mm_scfpyr_create(mm_scfpyr_t** out, int size, int height, int nbands, int scale_factor);
@@ -162,8 +164,21 @@ int mm_scfpyr_host_table(int size, int height, int nbands, int scale_factor, int
                          int* is_complex);
 /* outputs in the order of the reference's list, flattened: 0 = hi-pass residual, then
  * level-major bands (level 1 band 0 .. nbands-1, level 2 ...), last = low-pass residual */
+/* Host-side builder of the reconstruct multipliers, for testing (no GPU needed).  Output `index` (the build's order) gets
+ * a complex float64 table R ([side][side][2], same side / is_complex as mm_scfpyr_host_table) in FFT index order of its own
+ * grid, with the reference's whole mask chain back to the full grid (reconstruct angle mask x himask x i^(nbands-1) for
+ * bands; the lomask of every level it is embedded through; lo0mask, or hi0mask for the hi-pass residual) and 1/size^2
+ * folded in.  Convention, for coefficients c_o of one image:
+ *     C_o[a][b] = sum_{r,c} c_o[r][c] e^{-2 pi i (a r + b c)/side}          forward DFT, unnormalised
+ *     S[a'][b'] = sum_o C_o[a][b] R_o[a][b]     a' = (a < (side+1)/2 ? a : a - side) mod size, b' likewise (signed frequency)
+ *     out[y][x] = Re sum_{a,b} S[a][b] e^{+2 pi i (a y + b x)/size}          inverse DFT, unnormalised (1/size^2 is in R)
+ * out may be NULL to query side / is_complex only. */
+int mm_scfpyr_host_recon_table(int size, int height, int nbands, int scale_factor, int index, double* out, int* side,
+                               int* is_complex);
 int mm_scfpyr_num_outputs(const mm_scfpyr_t* h);
 int mm_scfpyr_output_info(const mm_scfpyr_t* h, int index, int* side, int* is_complex);
+/* workspace of mm_scfpyr_build and of mm_scfpyr_reconstruct alike: one n0 x n0 complex float64 spectrum per image, plus
+ * (size > 96) one intermediate plane of the same size per image */
 int64_t mm_scfpyr_workspace_bytes(const mm_scfpyr_t* h, int64_t n);
 /* images: device [n, size, size] float (precision 32) or double (precision 64) -- the reference's
  * [N,1,H,W] batch.  outputs: HOST array of mm_scfpyr_num_outputs device pointers; output i is
@@ -171,6 +186,12 @@ int64_t mm_scfpyr_workspace_bytes(const mm_scfpyr_t* h, int64_t n);
  * precision.  Internally float64 throughout. */
 int mm_scfpyr_build(const mm_scfpyr_t* h, const void* images, int precision, int64_t n, void* const* outputs,
                     void* workspace, int64_t workspace_bytes, void* stream);
+/* coeffs: HOST array of mm_scfpyr_num_outputs device pointers, in mm_scfpyr_build's output order and shapes (contiguous,
+ * `precision`); out: device [n, size, size] real image batch in the same precision.  Internally float64 throughout; results are
+ * deterministic (one workgroup per image, coefficients added in a fixed order).  Status codes as mm_scfpyr_build; n == 0 is a
+ * no-op. */
+int mm_scfpyr_reconstruct(const mm_scfpyr_t* h, void* const* coeffs, int precision, int64_t n, void* out, void* workspace,
+                          int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Convolutional networks (fp32 MFMA implicit-GEMM engine)

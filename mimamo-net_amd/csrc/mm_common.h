@@ -79,6 +79,11 @@ struct ScfOutput {
     std::vector<double> table;  // [side][side][2]
 };
 int build_scf_full_tables(int n0, int height, int nbands, int scale_factor, std::vector<ScfOutput>& outs);
+// The inverse (SCFpyr_PyTorch.reconstruct): per coefficient, in the same order and on the same grids, the complex float64
+// multiplier applied to that coefficient's own DFT (FFT order) before it is added into the n0 x n0 image spectrum at its
+// signed frequencies modulo n0 -- the whole mask chain back to the full grid, i^(nbands-1) for bands and the final
+// ifft's 1/n0^2 folded in.
+int build_scf_recon_tables(int n0, int height, int nbands, int scale_factor, std::vector<ScfOutput>& outs);
 
 }  // namespace mm
 

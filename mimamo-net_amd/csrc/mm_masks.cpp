@@ -147,9 +147,13 @@ int host_level_mask(const PyramidConfig& c, int level, int band, std::vector<dou
     }
 }
 
-// Walks SCFpyr_PyTorch.build / _build_levels (SCFpyr_PyTorch.py:70-208) once for an n0 x n0 grid and emits the
-// multiplier every returned tensor applies to the (shifted) image spectrum.
-int build_scf_full_tables(int n0, int height, int nbands, int scale_factor, std::vector<ScfOutput>& outs) {
+namespace {
+
+// Walks SCFpyr_PyTorch.build / _build_levels (SCFpyr_PyTorch.py:70-208) once for an n0 x n0 grid.  The low-pass chain
+// (lo0mask, then the lomask of every level a grid is cropped through) and himask are the same in reconstruct /
+// _reconstruct_levels (:214-318), which embeds each level back through the same crops; the two walks differ only in the
+// angle mask, the band factor and the normalisation, selected by `recon`.
+int scf_walk(int n0, int height, int nbands, int scale_factor, bool recon, std::vector<ScfOutput>& outs) {
     outs.clear();
     if (n0 <= 0 || height < 2 || nbands < 2 || scale_factor < 1) return MM_ERR_INVALID_ARG;
     Grid g = prepare_grid(n0);
@@ -166,11 +170,14 @@ int build_scf_full_tables(int n0, int height, int nbands, int scale_factor, std:
         double alpha = std::fmod(Xc[k] + kPi, 2 * kPi);
         if (alpha < 0) alpha += 2 * kPi;
         alpha -= kPi;
-        Yc[k] = 2 * std::sqrt(cst) * std::pow(std::cos(Xc[k]), order) * (std::fabs(alpha) < kPi / 2 ? 1.0 : 0.0);
+        if (recon)  // :267 -- no factor 2 and no half-plane cut
+            Yc[k] = std::sqrt(cst) * std::pow(std::cos(Xc[k]), order);
+        else
+            Yc[k] = 2 * std::sqrt(cst) * std::pow(std::cos(Xc[k]), order) * (std::fabs(alpha) < kPi / 2 ? 1.0 : 0.0);
     }
-    // (-i)^(nbands-1): exact values, the power cycles with period 4
+    // (-i)^(nbands-1) for build, i^(nbands-1) for reconstruct: exact values, the power cycles with period 4
     static const double fre[4] = {1, 0, -1, 0}, fim[4] = {0, -1, 0, 1};
-    const double cr = fre[order & 3], ci = fim[order & 3];
+    const double cr = fre[order & 3], ci = recon ? -fim[order & 3] : fim[order & 3];
 
     // emit: real multiplier `mk` on the shifted n x n grid -> complex table in FFT order
     auto emit = [&](const std::vector<double>& mk, int n, double re, double im, int is_complex) {
@@ -178,7 +185,8 @@ int build_scf_full_tables(int n0, int height, int nbands, int scale_factor, std:
         o.side = n;
         o.is_complex = is_complex;
         o.table.assign((size_t)n * n * 2, 0.0);
-        const double norm = 1.0 / ((double)n * n);
+        // build: each output's own ifft (1/side^2); reconstruct: the one ifft on the n0 grid (1/n0^2)
+        const double norm = recon ? 1.0 / ((double)n0 * n0) : 1.0 / ((double)n * n);
         for (int a = 0; a < n; ++a)
             for (int b = 0; b < n; ++b) {
                 const int u = (a + n / 2) % n, v = (b + n / 2) % n;  // fftshift (either parity: the DC sample lands on n / 2)
@@ -232,6 +240,16 @@ int build_scf_full_tables(int n0, int height, int nbands, int scale_factor, std:
     }
     emit(lo, n, 1.0, 0.0, 0);
     return MM_OK;
+}
+
+}  // namespace
+
+int build_scf_full_tables(int n0, int height, int nbands, int scale_factor, std::vector<ScfOutput>& outs) {
+    return scf_walk(n0, height, nbands, scale_factor, false, outs);
+}
+
+int build_scf_recon_tables(int n0, int height, int nbands, int scale_factor, std::vector<ScfOutput>& outs) {
+    return scf_walk(n0, height, nbands, scale_factor, true, outs);
 }
 
 int build_pyramid_tables(const PyramidConfig& c, PyramidTables& t) {

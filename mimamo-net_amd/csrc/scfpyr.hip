@@ -14,6 +14,14 @@
 //             (image, output o); T_o = the reference's mask product for that output on its (cropped) grid, in FFT
 //             order, with 1/m^2 and the (-i)^(nbands-1) band factor folded in (mm_masks.cpp); a' = a's signed
 //             frequency taken modulo n0 (the reference's centre crops of the shifted spectrum keep signed frequency).
+//
+// SCFpyr_PyTorch.reconstruct (api/steerable/SCFpyr_PyTorch.py:214-318) is linear in the coefficients, so it runs the same two kernels
+// the other way round on the same workspace:
+//   per coefficient o, in the build's output order, one launch of scf_forward_kernel on o's own m x m grid (complex input for
+//   bands) whose column pass ends in  S[a'][b'] (+)= DFT_m(c_o)[a][b] R_o[a][b]  -- R_o the reconstruct multiplier (mm_masks.cpp:
+//   mask chain, i^(nbands-1), 1/n0^2), a' as above; the hi-pass residual (m == n0, first) stores, every later one adds;
+//   then  out[y][x] = Re sum_{a,b} S[a][b] e^{+2 pi i (a y + b x)/n0}:  scf_inverse_kernel at m = n0 with a table of ones.
+// One workgroup per image and launches in a fixed order on one stream: deterministic, no atomics.
 #include <algorithm>
 #include <cmath>
 #include <new>
@@ -25,6 +33,8 @@ struct mm_scfpyr {
     int n_out;
     std::vector<int> side, is_complex;
     std::vector<double2*> d_table;  // per output, device
+    std::vector<double2*> d_rtable; // per output: its reconstruct multiplier (same side), device
+    double2* d_unit;                // [size][size] ones: the final inverse of reconstruct
     std::vector<double2*> d_tw;     // per output: e^{+2 pi i k / side}, [side] (outputs of one side share the table)
     std::vector<double2*> d_tw_own; // the distinct twiddle allocations
     double2* d_twiddle;             // [size]  e^{+2 pi i k / size}
@@ -37,45 +47,74 @@ constexpr int kScfThreads = 256;
 constexpr int kScfLdsSide = 96;   // LDS-resident intermediate: side^2 complex float64 = 147 456 B at 96
 constexpr int kScfMaxSide = 1024; // above kScfLdsSide the intermediate goes through a global scratch; O(side^3) per image: completeness, not speed
 
-template <typename TIn>
+// What the column pass of scf_forward_kernel does with each spectrum sample v = X[kr][kc] of the m x m input:
+enum ScfEpilogue {
+    kScfPlain = 0,   // build: F[kr][kc] = v                                          (m == n0)
+    kScfMulStore,    // reconstruct, first coefficient: S[kr'][kc'] = v * T[kr][kc]   (the hi-pass residual: m == n0, covers S)
+    kScfMulAdd,      // reconstruct, every later coefficient: S[kr'][kc'] += v * T[kr][kc]
+};                   // kr', kc' = the signed frequency of kr, kc modulo n0 (as in scf_inverse_kernel)
+
+template <typename TIn, bool kComplex, int kEpi>
 __global__ __launch_bounds__(kScfThreads) void scf_forward_kernel(const TIn* __restrict__ im, double2* __restrict__ F,
-                                                                  const double2* __restrict__ tw, int n0, double2* scratch) {
+                                                                  const double2* __restrict__ tw, int m, double2* scratch,
+                                                                  const double2* __restrict__ T, int n0) {
     extern __shared__ __attribute__((aligned(16))) double2 sm[];
-    double2* w = sm;                                                                     // [n0]
-    double2* X1 = scratch ? scratch + (size_t)blockIdx.x * n0 * n0 : sm + n0;           // [n0][n0] row transforms
-    for (int k = threadIdx.x; k < n0; k += kScfThreads) w[k] = tw[k];
+    double2* w = sm;                                                                     // [m]
+    double2* X1 = scratch ? scratch + (size_t)blockIdx.x * m * m : sm + m;              // [m][m] row transforms
+    for (int k = threadIdx.x; k < m; k += kScfThreads) w[k] = tw[k];
     __syncthreads();
-    const TIn* x = im + (size_t)blockIdx.x * n0 * n0;
-    for (int idx = threadIdx.x; idx < n0 * n0; idx += kScfThreads) {
-        const int r = idx / n0, k = idx - r * n0;
+    const TIn* x = im + (size_t)blockIdx.x * m * m * (kComplex ? 2 : 1);
+    for (int idx = threadIdx.x; idx < m * m; idx += kScfThreads) {
+        const int r = idx / m, k = idx - r * m;
         double re = 0.0, imv = 0.0;
         int j = 0;
-        for (int c = 0; c < n0; ++c) {
-            const double v = (double)x[r * n0 + c];
+        for (int c = 0; c < m; ++c) {
             const double2 t = w[j];
-            re = fma(v, t.x, re);
-            imv = fma(-v, t.y, imv);  // e^{-i...}
+            if (kComplex) {
+                // v * conj(t)
+                const double vr = (double)x[(size_t)(r * m + c) * 2], vi = (double)x[(size_t)(r * m + c) * 2 + 1];
+                re = fma(vr, t.x, fma(vi, t.y, re));
+                imv = fma(vi, t.x, fma(-vr, t.y, imv));
+            } else {
+                const double v = (double)x[r * m + c];
+                re = fma(v, t.x, re);
+                imv = fma(-v, t.y, imv);  // e^{-i...}
+            }
             j += k;
-            if (j >= n0) j -= n0;
+            if (j >= m) j -= m;
         }
         X1[idx] = make_double2(re, imv);
     }
     __syncthreads();
     double2* Fo = F + (size_t)blockIdx.x * n0 * n0;
-    for (int idx = threadIdx.x; idx < n0 * n0; idx += kScfThreads) {
-        const int kr = idx / n0, kc = idx - kr * n0;
+    const int h = (m + 1) / 2;
+    for (int idx = threadIdx.x; idx < m * m; idx += kScfThreads) {
+        const int kr = idx / m, kc = idx - kr * m;
         double re = 0.0, imv = 0.0;
         int j = 0;
-        for (int r = 0; r < n0; ++r) {
-            const double2 a = X1[r * n0 + kc];
+        for (int r = 0; r < m; ++r) {
+            const double2 a = X1[r * m + kc];
             const double2 t = w[j];
             // a * conj(t)
             re = fma(a.x, t.x, fma(a.y, t.y, re));
             imv = fma(a.y, t.x, fma(-a.x, t.y, imv));
             j += kr;
-            if (j >= n0) j -= n0;
+            if (j >= m) j -= m;
         }
-        Fo[idx] = make_double2(re, imv);
+        if (kEpi == kScfPlain) {
+            Fo[idx] = make_double2(re, imv);
+        } else {
+            const double2 t = T[idx];
+            const double pr = re * t.x - imv * t.y, pi = re * t.y + imv * t.x;
+            const int sa = kr < h ? kr : kr - m + n0, sb = kc < h ? kc : kc - m + n0;   // m <= n0: in [0, n0), one-to-one
+            double2* d = Fo + (size_t)sa * n0 + sb;
+            if (kEpi == kScfMulStore) {
+                *d = make_double2(pr, pi);
+            } else {
+                const double2 o = *d;
+                *d = make_double2(o.x + pr, o.y + pi);
+            }
+        }
     }
 }
 
@@ -169,13 +208,31 @@ int mm_scfpyr_host_table(int size, int height, int nbands, int scale_factor, int
     return MM_OK;
 }
 
+int mm_scfpyr_host_recon_table(int size, int height, int nbands, int scale_factor, int index, double* out, int* side,
+                               int* is_complex) {
+    if (!side || !is_complex) return MM_ERR_INVALID_ARG;
+    int rc = mm::scf_check(size, height, nbands, scale_factor);
+    if (rc != MM_OK) return rc;
+    std::vector<mm::ScfOutput> outs;
+    rc = mm::build_scf_recon_tables(size, height, nbands, scale_factor, outs);
+    if (rc != MM_OK) return rc;
+    if (index < 0 || index >= (int)outs.size()) return MM_ERR_INVALID_ARG;
+    *side = outs[index].side;
+    *is_complex = outs[index].is_complex;
+    if (out)
+        for (size_t i = 0; i < outs[index].table.size(); ++i) out[i] = outs[index].table[i];
+    return MM_OK;
+}
+
 int mm_scfpyr_create(mm_scfpyr_t** out, int size, int height, int nbands, int scale_factor) {
     if (!out) return MM_ERR_INVALID_ARG;
     *out = nullptr;
     int rc = mm::scf_check(size, height, nbands, scale_factor);
     if (rc != MM_OK) return rc;
-    std::vector<mm::ScfOutput> outs;
+    std::vector<mm::ScfOutput> outs, routs;
     rc = mm::build_scf_full_tables(size, height, nbands, scale_factor, outs);
+    if (rc != MM_OK) return rc;
+    rc = mm::build_scf_recon_tables(size, height, nbands, scale_factor, routs);
     if (rc != MM_OK) return rc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return MM_ERR_NO_DEVICE;
@@ -184,6 +241,7 @@ int mm_scfpyr_create(mm_scfpyr_t** out, int size, int height, int nbands, int sc
     h->size = size; h->height = height; h->nbands = nbands; h->scale_factor = scale_factor;
     h->n_out = (int)outs.size();
     h->d_twiddle = nullptr;
+    h->d_unit = nullptr;
     hipError_t e = hipGetDevice(&h->device);
     for (size_t i = 0; i < outs.size() && e == hipSuccess; ++i) {
         double2* d = nullptr;
@@ -194,6 +252,20 @@ int mm_scfpyr_create(mm_scfpyr_t** out, int size, int height, int nbands, int sc
             h->is_complex.push_back(outs[i].is_complex);
             e = hipMemcpy(d, outs[i].table.data(), outs[i].table.size() * sizeof(double), hipMemcpyHostToDevice);
         }
+    }
+    for (size_t i = 0; i < routs.size() && e == hipSuccess; ++i) {
+        double2* d = nullptr;
+        e = hipMalloc((void**)&d, routs[i].table.size() * sizeof(double));
+        if (e == hipSuccess) {
+            h->d_rtable.push_back(d);
+            e = hipMemcpy(d, routs[i].table.data(), routs[i].table.size() * sizeof(double), hipMemcpyHostToDevice);
+        }
+    }
+    if (e == hipSuccess) {
+        std::vector<double> ones((size_t)size * size * 2, 0.0);
+        for (size_t k = 0; k < ones.size(); k += 2) ones[k] = 1.0;
+        e = hipMalloc((void**)&h->d_unit, ones.size() * sizeof(double));
+        if (e == hipSuccess) e = hipMemcpy(h->d_unit, ones.data(), ones.size() * sizeof(double), hipMemcpyHostToDevice);
     }
     auto upload_twiddle = [&](int n, double2** dst) {
         std::vector<double> tw((size_t)n * 2);
@@ -243,9 +315,12 @@ int mm_scfpyr_destroy(mm_scfpyr_t* h) {
     if (!h) return MM_OK;
     for (double2* d : h->d_table)
         if (d) (void)hipFree(d);
+    for (double2* d : h->d_rtable)
+        if (d) (void)hipFree(d);
     for (double2* d : h->d_tw_own)
         if (d) (void)hipFree(d);
     if (h->d_twiddle) (void)hipFree(h->d_twiddle);
+    if (h->d_unit) (void)hipFree(h->d_unit);
     delete h;
     return MM_OK;
 }
@@ -286,11 +361,13 @@ int mm_scfpyr_build(const mm_scfpyr_t* h, const void* images, int precision, int
     const dim3 grid((unsigned)n), block(mm::kScfThreads);
     int rc;
     if (precision == 32) {
-        if ((rc = mm::raise_lds(mm::scf_forward_kernel<float>, lds_f)) != MM_OK) return rc;
-        hipLaunchKernelGGL(mm::scf_forward_kernel<float>, grid, block, lds_f, s, (const float*)images, F, h->d_twiddle, n0, scratch);
+        auto k = mm::scf_forward_kernel<float, false, mm::kScfPlain>;
+        if ((rc = mm::raise_lds(k, lds_f)) != MM_OK) return rc;
+        hipLaunchKernelGGL(k, grid, block, lds_f, s, (const float*)images, F, h->d_twiddle, n0, scratch, nullptr, n0);
     } else {
-        if ((rc = mm::raise_lds(mm::scf_forward_kernel<double>, lds_f)) != MM_OK) return rc;
-        hipLaunchKernelGGL(mm::scf_forward_kernel<double>, grid, block, lds_f, s, (const double*)images, F, h->d_twiddle, n0, scratch);
+        auto k = mm::scf_forward_kernel<double, false, mm::kScfPlain>;
+        if ((rc = mm::raise_lds(k, lds_f)) != MM_OK) return rc;
+        hipLaunchKernelGGL(k, grid, block, lds_f, s, (const double*)images, F, h->d_twiddle, n0, scratch, nullptr, n0);
     }
     MM_LAUNCH_CHECK();
     for (int i = 0; i < h->n_out; ++i) {
@@ -309,6 +386,62 @@ int mm_scfpyr_build(const mm_scfpyr_t* h, const void* images, int precision, int
         }
         MM_LAUNCH_CHECK();
     }
+    return MM_OK;
+}
+
+int mm_scfpyr_reconstruct(const mm_scfpyr_t* h, void* const* coeffs, int precision, int64_t n, void* out, void* workspace,
+                          int64_t workspace_bytes, void* stream) {
+    if (!h || (precision != 32 && precision != 64) || n < 0) return MM_ERR_INVALID_ARG;
+    if (n == 0) return MM_OK;
+    if (!coeffs || !out || !workspace) return MM_ERR_INVALID_ARG;
+    if (workspace_bytes < mm_scfpyr_workspace_bytes(h, n)) return MM_ERR_WORKSPACE;
+    for (int i = 0; i < h->n_out; ++i)
+        if (!coeffs[i]) return MM_ERR_INVALID_ARG;
+    MM_CHECK_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    double2* S = (double2*)workspace;   // [n][n0][n0] image spectrum, accumulated coefficient by coefficient
+    const int n0 = h->size;
+    double2* scratch = n0 > mm::kScfLdsSide ? S + (size_t)n * n0 * n0 : nullptr;   // [n][n0][n0], reused by every launch
+    const size_t lds_max = std::max(((size_t)mm::kScfLdsSide * mm::kScfLdsSide + mm::kScfLdsSide) * sizeof(double2),
+                                    (size_t)mm::kScfMaxSide * sizeof(double2));
+    const dim3 grid((unsigned)n), block(mm::kScfThreads);
+    int rc;
+    // the hi-pass residual comes first and covers the whole n0 grid: it initialises S, so no memset and no float atomics
+    for (int i = 0; i < h->n_out; ++i) {
+        const int m = h->side[i];
+        double2* sc = m > mm::kScfLdsSide ? scratch : nullptr;
+        const size_t lds_i = ((sc ? 0 : (size_t)m * m) + m) * sizeof(double2);
+        const bool first = i == 0, cplx = h->is_complex[i] != 0;
+        auto launch = [&](auto kernel, auto in) -> int {
+            if ((rc = mm::raise_lds(kernel, lds_max)) != MM_OK) return rc;
+            hipLaunchKernelGGL(kernel, grid, block, lds_i, s, in, S, h->d_tw[i], m, sc, h->d_rtable[i], n0);
+            MM_LAUNCH_CHECK();
+            return MM_OK;
+        };
+        if (precision == 32) {
+            const float* in = (const float*)coeffs[i];
+            if (first) rc = launch(mm::scf_forward_kernel<float, false, mm::kScfMulStore>, in);
+            else if (cplx) rc = launch(mm::scf_forward_kernel<float, true, mm::kScfMulAdd>, in);
+            else rc = launch(mm::scf_forward_kernel<float, false, mm::kScfMulAdd>, in);
+        } else {
+            const double* in = (const double*)coeffs[i];
+            if (first) rc = launch(mm::scf_forward_kernel<double, false, mm::kScfMulStore>, in);
+            else if (cplx) rc = launch(mm::scf_forward_kernel<double, true, mm::kScfMulAdd>, in);
+            else rc = launch(mm::scf_forward_kernel<double, false, mm::kScfMulAdd>, in);
+        }
+        if (rc != MM_OK) return rc;
+    }
+    const size_t lds_f = ((scratch ? 0 : (size_t)n0 * n0) + n0) * sizeof(double2);
+    if (precision == 32) {
+        if ((rc = mm::raise_lds(mm::scf_inverse_kernel<float>, lds_max)) != MM_OK) return rc;
+        hipLaunchKernelGGL(mm::scf_inverse_kernel<float>, grid, block, lds_f, s, S, h->d_unit, h->d_twiddle, (float*)out, n0, n0,
+                           0, scratch);
+    } else {
+        if ((rc = mm::raise_lds(mm::scf_inverse_kernel<double>, lds_max)) != MM_OK) return rc;
+        hipLaunchKernelGGL(mm::scf_inverse_kernel<double>, grid, block, lds_f, s, S, h->d_unit, h->d_twiddle, (double*)out, n0, n0,
+                           0, scratch);
+    }
+    MM_LAUNCH_CHECK();
     return MM_OK;
 }
 

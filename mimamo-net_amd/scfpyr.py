@@ -1,10 +1,10 @@
-"""SCFpyr_PyTorch on MI355X -- drop-in for api/steerable/SCFpyr_PyTorch.py:51-208 (construction only).
+"""SCFpyr_PyTorch on MI355X -- drop-in for api/steerable/SCFpyr_PyTorch.py:51-318.
 
 `build(im_batch)` returns the reference's full list `[hi, [band_0..band_{nbands-1}], ..., lo]` for arbitrary
-square images; the arithmetic runs in libmimamo_hip.so (csrc/scfpyr.hip: DFT-by-summation with float64
-accumulation).  The inference pipeline does not use this class -- Phase_Difference_Extractor.build_pyramid calls
-the mirrored-input kernel of csrc/pyramid.hip, which produces only the coefficients the phase stage keeps.
-`reconstruct` (SCFpyr_PyTorch.py:213-318) is never reached by inference and is not implemented.
+square images, and `reconstruct(coeff)` turns such a list -- edited or not -- back into the image batch `[N,H,W]`;
+the arithmetic runs in libmimamo_hip.so (csrc/scfpyr.hip: DFT-by-summation with float64 accumulation).  The
+inference pipeline does not use this class -- Phase_Difference_Extractor.build_pyramid calls the mirrored-input
+kernel of csrc/pyramid.hip, which produces only the coefficients the phase stage keeps.
 """
 import ctypes
 
@@ -54,6 +54,15 @@ class SCFpyr_PyTorch(object):
         except Exception:
             pass
 
+    def _output_shapes(self, h, n):
+        L = _lib.lib()
+        side, cplx = ctypes.c_int(), ctypes.c_int()
+        shapes = []
+        for i in range(L.mm_scfpyr_num_outputs(h)):
+            _lib.check(L.mm_scfpyr_output_info(h, i, ctypes.byref(side), ctypes.byref(cplx)), "mm_scfpyr_output_info")
+            shapes.append((n, side.value, side.value, 2) if cplx.value else (n, side.value, side.value))
+        return shapes
+
     def build(self, im_batch):
         """im_batch [N,1,H,W] -> [hi [N,H,W], [bands [N,h,w,2]] per level ..., lo [N,h',w']]  (SCFpyr_PyTorch.py:70-125)."""
         assert im_batch.device == self.device, 'Devices invalid (pyr = {}, batch = {})'.format(self.device, im_batch.device)
@@ -65,13 +74,8 @@ class SCFpyr_PyTorch(object):
             raise NotImplementedError("square images only (SCFpyr_PyTorch.py:87 swaps height and width)")
         h = self._get(hh)
         L = _lib.lib()
-        n_out = L.mm_scfpyr_num_outputs(h)
-        outs = []
-        side, cplx = ctypes.c_int(), ctypes.c_int()
-        for i in range(n_out):
-            _lib.check(L.mm_scfpyr_output_info(h, i, ctypes.byref(side), ctypes.byref(cplx)), "mm_scfpyr_output_info")
-            shape = (n, side.value, side.value, 2) if cplx.value else (n, side.value, side.value)
-            outs.append(torch.empty(shape, dtype=self.dtype, device=self.device))
+        outs = [torch.empty(shape, dtype=self.dtype, device=self.device) for shape in self._output_shapes(h, n)]
+        n_out = len(outs)
         ws_bytes = L.mm_scfpyr_workspace_bytes(h, n)
         ws = torch.empty((max(ws_bytes, 8) // 8,), dtype=torch.float64, device=self.device)
         ptrs = (ctypes.c_void_p * n_out)(*[o.data_ptr() for o in outs])
@@ -86,3 +90,40 @@ class SCFpyr_PyTorch(object):
             k += self.nbands
         coeff.append(outs[k])
         return coeff
+
+    def reconstruct(self, coeff):
+        """coeff = a list as build returns it, possibly edited -> the real image batch [N,H,W] in the pyramid's dtype on its
+        device (SCFpyr_PyTorch.py:214-318).  Deliberate difference: with height 2 the list is [hi, lo] and the reference
+        compares nbands with len(lo), the batch size (:216); here any batch size is accepted."""
+        if not isinstance(coeff, (list, tuple)) or len(coeff) != self.height:
+            raise ValueError("reconstruct: expected a list of {} levels (hi, {} band levels, lo)".format(
+                self.height, self.height - 2))
+        for level in coeff[1:-1]:
+            if not isinstance(level, (list, tuple)) or len(level) != self.nbands:
+                raise Exception("Unmatched number of orientations")
+        flat = [coeff[0]] + [b for level in coeff[1:-1] for b in level] + [coeff[-1]]
+        for c in flat:
+            if not isinstance(c, torch.Tensor):
+                raise ValueError("reconstruct: coefficients must be tensors")
+            assert c.device == self.device, 'Devices invalid (pyr = {}, batch = {})'.format(self.device, c.device)
+            assert c.dtype == self.dtype, 'Image batch must be torch.float{}'.format(self.precision)
+        hi = flat[0]
+        if hi.dim() != 3 or hi.shape[1] != hi.shape[2]:
+            raise ValueError("reconstruct: the hi-pass residual must be [N,H,H], got {}".format(tuple(hi.shape)))
+        n, size = hi.shape[0], hi.shape[1]
+        h = self._get(size)
+        shapes = self._output_shapes(h, n)
+        for i, (c, shape) in enumerate(zip(flat, shapes)):
+            if tuple(c.shape) != shape:
+                raise ValueError("reconstruct: coefficient {} has shape {}, expected {}".format(i, tuple(c.shape), shape))
+        out = torch.empty((n, size, size), dtype=self.dtype, device=self.device)
+        L = _lib.lib()
+        ws_bytes = L.mm_scfpyr_workspace_bytes(h, n)
+        ws = torch.empty((max(ws_bytes, 8) // 8,), dtype=torch.float64, device=self.device)
+        flat = [c.contiguous() for c in flat]
+        ptrs = (ctypes.c_void_p * len(flat))(*[c.data_ptr() for c in flat])
+        with torch.cuda.device(self.device):
+            rc = L.mm_scfpyr_reconstruct(h, ptrs, self.precision, n, _lib.ptr(out), _lib.ptr(ws), ws_bytes,
+                                         _lib.current_stream())
+        _lib.check(rc, "mm_scfpyr_reconstruct")
+        return out
