@@ -192,6 +192,25 @@ int mm_scfpyr_build(const mm_scfpyr_t* h, const void* images, int precision, int
  * no-op. */
 int mm_scfpyr_reconstruct(const mm_scfpyr_t* h, void* const* coeffs, int precision, int64_t n, void* out, void* workspace,
                           int64_t workspace_bytes, void* stream);
+/* Vector-Jacobian products of mm_scfpyr_build / mm_scfpyr_reconstruct (both operators are linear): the gradients autograd
+ * needs, each computed by the opposite direction's launch sequence with the tables conjugated.  T_o is output o's build
+ * multiplier (mm_scfpyr_host_table), R_o its reconstruct multiplier (mm_scfpyr_host_recon_table), m its side, n0 = size,
+ * a' the signed frequency of a modulo n0 as above.  For one image:
+ *   build adjoint       (grad_coeffs g_o -> grad_images gx; g_o real for the residuals, re/im pairs for the bands):
+ *     G_o[a][b]  = sum_{r,c} g_o[r][c] e^{-2 pi i (a r + b c)/m}
+ *     S[a'][b']  = sum_o conj(T_o[a][b]) G_o[a][b]
+ *     gx[y][x]   = Re sum_{a,b} S[a][b] e^{+2 pi i (a y + b x)/n0}
+ *   reconstruct adjoint (grad_image gy -> grad_coeffs g_o):
+ *     Y[a][b]    = sum_{r,c} gy[r][c] e^{-2 pi i (a r + b c)/n0}
+ *     g_o[r][c]  = sum_{a,b} conj(R_o[a][b]) Y[a'][b'] e^{+2 pi i (a r + b c)/m}   (real part for the residuals)
+ * For a band stored as [...,2] the gradient of the (re, im) pair is (Re, Im) of the complex adjoint.  grad_images /
+ * grad_image: device [n, size, size]; grad_coeffs: HOST array of mm_scfpyr_num_outputs device pointers in the build's order
+ * and shapes (contiguous).  Precision, workspace (mm_scfpyr_workspace_bytes), status codes and null checks as
+ * mm_scfpyr_build / mm_scfpyr_reconstruct; n == 0 is a no-op; deterministic.  Added without an MM_VERSION change (still 106). */
+int mm_scfpyr_build_adjoint(const mm_scfpyr_t* h, void* const* grad_coeffs, int precision, int64_t n, void* grad_images,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+int mm_scfpyr_reconstruct_adjoint(const mm_scfpyr_t* h, const void* grad_image, int precision, int64_t n,
+                                  void* const* grad_coeffs, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Convolutional networks (fp32 MFMA implicit-GEMM engine)

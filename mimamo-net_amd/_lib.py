@@ -46,6 +46,8 @@ SIGNATURES = {
     "mm_scfpyr_build": (_i, [_vp, _vp, _i, _i64, _c.POINTER(_vp), _vp, _i64, _vp]),
     "mm_scfpyr_host_recon_table": (_i, [_i, _i, _i, _i, _i, _c.POINTER(_c.c_double), _c.POINTER(_i), _c.POINTER(_i)]),
     "mm_scfpyr_reconstruct": (_i, [_vp, _c.POINTER(_vp), _i, _i64, _vp, _vp, _i64, _vp]),
+    "mm_scfpyr_build_adjoint": (_i, [_vp, _c.POINTER(_vp), _i, _i64, _vp, _vp, _i64, _vp]),
+    "mm_scfpyr_reconstruct_adjoint": (_i, [_vp, _vp, _i, _i64, _c.POINTER(_vp), _vp, _i64, _vp]),
     "mm_preproc_host_coeffs": (_i, [_i, _i, _i, _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i), _i]),
     "mm_preproc_create": (_i, [_c.POINTER(_vp), _i, _i, _i, _i, _c.POINTER(_f)]),
     "mm_preproc_destroy": (_i, [_vp]),

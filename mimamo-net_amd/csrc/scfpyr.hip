@@ -22,6 +22,11 @@
 //   mask chain, i^(nbands-1), 1/n0^2), a' as above; the hi-pass residual (m == n0, first) stores, every later one adds;
 //   then  out[y][x] = Re sum_{a,b} S[a][b] e^{+2 pi i (a y + b x)/n0}:  scf_inverse_kernel at m = n0 with a table of ones.
 // One workgroup per image and launches in a fixed order on one stream: deterministic, no atomics.
+//
+// Both operators are linear, and each one's adjoint (vector-Jacobian product) is the other one's launch sequence with the
+// table conjugated where it is loaded (kConjT; no second set of tables is uploaded):
+//   build adjoint       : S[a'][b'] = sum_o conj(T_o[a][b]) DFT_m(g_o)[a][b],  grad_x = Re sum_{a,b} S e^{+...}   (reconstruct's launches)
+//   reconstruct adjoint : g_o = sum_{a,b} conj(R_o[a][b]) DFT_n0(g_y)[a'][b'] e^{+...}, real for the residuals  (build's launches)
 #include <algorithm>
 #include <cmath>
 #include <new>
@@ -54,7 +59,7 @@ enum ScfEpilogue {
     kScfMulAdd,      // reconstruct, every later coefficient: S[kr'][kc'] += v * T[kr][kc]
 };                   // kr', kc' = the signed frequency of kr, kc modulo n0 (as in scf_inverse_kernel)
 
-template <typename TIn, bool kComplex, int kEpi>
+template <typename TIn, bool kComplex, int kEpi, bool kConjT = false>   // kConjT: multiply by conj(T) (the adjoint passes)
 __global__ __launch_bounds__(kScfThreads) void scf_forward_kernel(const TIn* __restrict__ im, double2* __restrict__ F,
                                                                   const double2* __restrict__ tw, int m, double2* scratch,
                                                                   const double2* __restrict__ T, int n0) {
@@ -104,7 +109,8 @@ __global__ __launch_bounds__(kScfThreads) void scf_forward_kernel(const TIn* __r
         if (kEpi == kScfPlain) {
             Fo[idx] = make_double2(re, imv);
         } else {
-            const double2 t = T[idx];
+            double2 t = T[idx];
+            if (kConjT) t.y = -t.y;
             const double pr = re * t.x - imv * t.y, pi = re * t.y + imv * t.x;
             const int sa = kr < h ? kr : kr - m + n0, sb = kc < h ? kc : kc - m + n0;   // m <= n0: in [0, n0), one-to-one
             double2* d = Fo + (size_t)sa * n0 + sb;
@@ -118,7 +124,7 @@ __global__ __launch_bounds__(kScfThreads) void scf_forward_kernel(const TIn* __r
     }
 }
 
-template <typename TOut>
+template <typename TOut, bool kConjT = false>   // kConjT: multiply by conj(T) (the adjoint passes)
 __global__ __launch_bounds__(kScfThreads) void scf_inverse_kernel(const double2* __restrict__ F, const double2* __restrict__ T,
                                                                   const double2* __restrict__ tw, TOut* __restrict__ out,
                                                                   int n0, int m, int is_complex, double2* scratch) {
@@ -138,7 +144,9 @@ __global__ __launch_bounds__(kScfThreads) void scf_inverse_kernel(const double2*
         int j = 0;
         for (int b = 0; b < m; ++b) {
             const int sb = b < h ? b : b - m + n0;
-            const double2 f = Frow[sb], t = Trow[b];
+            const double2 f = Frow[sb];
+            double2 t = Trow[b];
+            if (kConjT) t.y = -t.y;
             const double sr = f.x * t.x - f.y * t.y, si = f.x * t.y + f.y * t.x;
             const double2 e = w[j];
             re = fma(sr, e.x, fma(-si, e.y, re));
@@ -340,8 +348,16 @@ int64_t mm_scfpyr_workspace_bytes(const mm_scfpyr_t* h, int64_t n) {
     return n * (int64_t)h->size * h->size * (int64_t)sizeof(double2) * (h->size > mm::kScfLdsSide ? 2 : 1);
 }
 
-int mm_scfpyr_build(const mm_scfpyr_t* h, const void* images, int precision, int64_t n, void* const* outputs,
-                    void* workspace, int64_t workspace_bytes, void* stream) {
+}  // extern "C"
+
+namespace mm {
+namespace {
+
+// image -> coefficients: the build (tables = the build multipliers T_o) or, with kConjT, the adjoint of reconstruct (tables =
+// the reconstruct multipliers R_o, applied conjugated).  images [n][n0][n0] real; outputs in the build's order and shapes.
+template <bool kConjT>
+int scf_image_to_coeffs(const mm_scfpyr_t* h, const std::vector<double2*>& tables, const void* images, int precision, int64_t n,
+                        void* const* outputs, void* workspace, int64_t workspace_bytes, void* stream) {
     if (!h || (precision != 32 && precision != 64) || n < 0) return MM_ERR_INVALID_ARG;
     if (n == 0) return MM_OK;
     if (!images || !outputs || !workspace) return MM_ERR_INVALID_ARG;
@@ -352,36 +368,36 @@ int mm_scfpyr_build(const mm_scfpyr_t* h, const void* images, int precision, int
     hipStream_t s = (hipStream_t)stream;
     double2* F = (double2*)workspace;
     const int n0 = h->size;
-    double2* scratch = n0 > mm::kScfLdsSide ? F + (size_t)n * n0 * n0 : nullptr;   // [n][n0][n0], reused by every launch
+    double2* scratch = n0 > kScfLdsSide ? F + (size_t)n * n0 * n0 : nullptr;   // [n][n0][n0], reused by every launch
     auto lds_bytes = [&](int m) { return ((scratch ? 0 : (size_t)m * m) + m) * sizeof(double2); };
     const size_t lds_f = lds_bytes(n0);
     // the largest request of any launch: an LDS-resident level (side <= 96: intermediate + twiddles) or the twiddles of the largest side
-    const size_t lds_max = std::max(((size_t)mm::kScfLdsSide * mm::kScfLdsSide + mm::kScfLdsSide) * sizeof(double2),
-                                    (size_t)mm::kScfMaxSide * sizeof(double2));
-    const dim3 grid((unsigned)n), block(mm::kScfThreads);
+    const size_t lds_max = std::max(((size_t)kScfLdsSide * kScfLdsSide + kScfLdsSide) * sizeof(double2),
+                                    (size_t)kScfMaxSide * sizeof(double2));
+    const dim3 grid((unsigned)n), block(kScfThreads);
     int rc;
     if (precision == 32) {
-        auto k = mm::scf_forward_kernel<float, false, mm::kScfPlain>;
-        if ((rc = mm::raise_lds(k, lds_f)) != MM_OK) return rc;
+        auto k = scf_forward_kernel<float, false, kScfPlain>;
+        if ((rc = raise_lds(k, lds_f)) != MM_OK) return rc;
         hipLaunchKernelGGL(k, grid, block, lds_f, s, (const float*)images, F, h->d_twiddle, n0, scratch, nullptr, n0);
     } else {
-        auto k = mm::scf_forward_kernel<double, false, mm::kScfPlain>;
-        if ((rc = mm::raise_lds(k, lds_f)) != MM_OK) return rc;
+        auto k = scf_forward_kernel<double, false, kScfPlain>;
+        if ((rc = raise_lds(k, lds_f)) != MM_OK) return rc;
         hipLaunchKernelGGL(k, grid, block, lds_f, s, (const double*)images, F, h->d_twiddle, n0, scratch, nullptr, n0);
     }
     MM_LAUNCH_CHECK();
     for (int i = 0; i < h->n_out; ++i) {
         const int m = h->side[i];
         // a level whose grid fits keeps its intermediate in LDS even when the full-size levels do not
-        double2* sc = m > mm::kScfLdsSide ? scratch : nullptr;
+        double2* sc = m > kScfLdsSide ? scratch : nullptr;
         const size_t lds_i = ((sc ? 0 : (size_t)m * m) + m) * sizeof(double2);
         if (precision == 32) {
-            if ((rc = mm::raise_lds(mm::scf_inverse_kernel<float>, lds_max)) != MM_OK) return rc;
-            hipLaunchKernelGGL(mm::scf_inverse_kernel<float>, grid, block, lds_i, s, F, h->d_table[i], h->d_tw[i],
+            if ((rc = raise_lds(scf_inverse_kernel<float, kConjT>, lds_max)) != MM_OK) return rc;
+            hipLaunchKernelGGL((scf_inverse_kernel<float, kConjT>), grid, block, lds_i, s, F, tables[i], h->d_tw[i],
                                (float*)outputs[i], n0, m, h->is_complex[i], sc);
         } else {
-            if ((rc = mm::raise_lds(mm::scf_inverse_kernel<double>, lds_max)) != MM_OK) return rc;
-            hipLaunchKernelGGL(mm::scf_inverse_kernel<double>, grid, block, lds_i, s, F, h->d_table[i], h->d_tw[i],
+            if ((rc = raise_lds(scf_inverse_kernel<double, kConjT>, lds_max)) != MM_OK) return rc;
+            hipLaunchKernelGGL((scf_inverse_kernel<double, kConjT>), grid, block, lds_i, s, F, tables[i], h->d_tw[i],
                                (double*)outputs[i], n0, m, h->is_complex[i], sc);
         }
         MM_LAUNCH_CHECK();
@@ -389,8 +405,11 @@ int mm_scfpyr_build(const mm_scfpyr_t* h, const void* images, int precision, int
     return MM_OK;
 }
 
-int mm_scfpyr_reconstruct(const mm_scfpyr_t* h, void* const* coeffs, int precision, int64_t n, void* out, void* workspace,
-                          int64_t workspace_bytes, void* stream) {
+// coefficients -> image: the reconstruct (tables = R_o) or, with kConjT, the adjoint of the build (tables = T_o, applied
+// conjugated).  coeffs in the build's order and shapes; out [n][n0][n0] real.
+template <bool kConjT>
+int scf_coeffs_to_image(const mm_scfpyr_t* h, const std::vector<double2*>& tables, void* const* coeffs, int precision, int64_t n,
+                        void* out, void* workspace, int64_t workspace_bytes, void* stream) {
     if (!h || (precision != 32 && precision != 64) || n < 0) return MM_ERR_INVALID_ARG;
     if (n == 0) return MM_OK;
     if (!coeffs || !out || !workspace) return MM_ERR_INVALID_ARG;
@@ -401,48 +420,80 @@ int mm_scfpyr_reconstruct(const mm_scfpyr_t* h, void* const* coeffs, int precisi
     hipStream_t s = (hipStream_t)stream;
     double2* S = (double2*)workspace;   // [n][n0][n0] image spectrum, accumulated coefficient by coefficient
     const int n0 = h->size;
-    double2* scratch = n0 > mm::kScfLdsSide ? S + (size_t)n * n0 * n0 : nullptr;   // [n][n0][n0], reused by every launch
-    const size_t lds_max = std::max(((size_t)mm::kScfLdsSide * mm::kScfLdsSide + mm::kScfLdsSide) * sizeof(double2),
-                                    (size_t)mm::kScfMaxSide * sizeof(double2));
-    const dim3 grid((unsigned)n), block(mm::kScfThreads);
+    double2* scratch = n0 > kScfLdsSide ? S + (size_t)n * n0 * n0 : nullptr;   // [n][n0][n0], reused by every launch
+    const size_t lds_max = std::max(((size_t)kScfLdsSide * kScfLdsSide + kScfLdsSide) * sizeof(double2),
+                                    (size_t)kScfMaxSide * sizeof(double2));
+    const dim3 grid((unsigned)n), block(kScfThreads);
     int rc;
     // the hi-pass residual comes first and covers the whole n0 grid: it initialises S, so no memset and no float atomics
     for (int i = 0; i < h->n_out; ++i) {
         const int m = h->side[i];
-        double2* sc = m > mm::kScfLdsSide ? scratch : nullptr;
+        double2* sc = m > kScfLdsSide ? scratch : nullptr;
         const size_t lds_i = ((sc ? 0 : (size_t)m * m) + m) * sizeof(double2);
         const bool first = i == 0, cplx = h->is_complex[i] != 0;
         auto launch = [&](auto kernel, auto in) -> int {
-            if ((rc = mm::raise_lds(kernel, lds_max)) != MM_OK) return rc;
-            hipLaunchKernelGGL(kernel, grid, block, lds_i, s, in, S, h->d_tw[i], m, sc, h->d_rtable[i], n0);
+            if ((rc = raise_lds(kernel, lds_max)) != MM_OK) return rc;
+            hipLaunchKernelGGL(kernel, grid, block, lds_i, s, in, S, h->d_tw[i], m, sc, tables[i], n0);
             MM_LAUNCH_CHECK();
             return MM_OK;
         };
         if (precision == 32) {
             const float* in = (const float*)coeffs[i];
-            if (first) rc = launch(mm::scf_forward_kernel<float, false, mm::kScfMulStore>, in);
-            else if (cplx) rc = launch(mm::scf_forward_kernel<float, true, mm::kScfMulAdd>, in);
-            else rc = launch(mm::scf_forward_kernel<float, false, mm::kScfMulAdd>, in);
+            if (first) rc = launch(scf_forward_kernel<float, false, kScfMulStore, kConjT>, in);
+            else if (cplx) rc = launch(scf_forward_kernel<float, true, kScfMulAdd, kConjT>, in);
+            else rc = launch(scf_forward_kernel<float, false, kScfMulAdd, kConjT>, in);
         } else {
             const double* in = (const double*)coeffs[i];
-            if (first) rc = launch(mm::scf_forward_kernel<double, false, mm::kScfMulStore>, in);
-            else if (cplx) rc = launch(mm::scf_forward_kernel<double, true, mm::kScfMulAdd>, in);
-            else rc = launch(mm::scf_forward_kernel<double, false, mm::kScfMulAdd>, in);
+            if (first) rc = launch(scf_forward_kernel<double, false, kScfMulStore, kConjT>, in);
+            else if (cplx) rc = launch(scf_forward_kernel<double, true, kScfMulAdd, kConjT>, in);
+            else rc = launch(scf_forward_kernel<double, false, kScfMulAdd, kConjT>, in);
         }
         if (rc != MM_OK) return rc;
     }
+    // the final inverse multiplies by ones, which conjugation leaves alone: one instantiation serves both directions
     const size_t lds_f = ((scratch ? 0 : (size_t)n0 * n0) + n0) * sizeof(double2);
     if (precision == 32) {
-        if ((rc = mm::raise_lds(mm::scf_inverse_kernel<float>, lds_max)) != MM_OK) return rc;
-        hipLaunchKernelGGL(mm::scf_inverse_kernel<float>, grid, block, lds_f, s, S, h->d_unit, h->d_twiddle, (float*)out, n0, n0,
+        if ((rc = raise_lds(scf_inverse_kernel<float>, lds_max)) != MM_OK) return rc;
+        hipLaunchKernelGGL(scf_inverse_kernel<float>, grid, block, lds_f, s, S, h->d_unit, h->d_twiddle, (float*)out, n0, n0,
                            0, scratch);
     } else {
-        if ((rc = mm::raise_lds(mm::scf_inverse_kernel<double>, lds_max)) != MM_OK) return rc;
-        hipLaunchKernelGGL(mm::scf_inverse_kernel<double>, grid, block, lds_f, s, S, h->d_unit, h->d_twiddle, (double*)out, n0, n0,
+        if ((rc = raise_lds(scf_inverse_kernel<double>, lds_max)) != MM_OK) return rc;
+        hipLaunchKernelGGL(scf_inverse_kernel<double>, grid, block, lds_f, s, S, h->d_unit, h->d_twiddle, (double*)out, n0, n0,
                            0, scratch);
     }
     MM_LAUNCH_CHECK();
     return MM_OK;
+}
+
+}  // namespace
+}  // namespace mm
+
+extern "C" {
+
+int mm_scfpyr_build(const mm_scfpyr_t* h, const void* images, int precision, int64_t n, void* const* outputs,
+                    void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!h) return MM_ERR_INVALID_ARG;
+    return mm::scf_image_to_coeffs<false>(h, h->d_table, images, precision, n, outputs, workspace, workspace_bytes, stream);
+}
+
+int mm_scfpyr_reconstruct(const mm_scfpyr_t* h, void* const* coeffs, int precision, int64_t n, void* out, void* workspace,
+                          int64_t workspace_bytes, void* stream) {
+    if (!h) return MM_ERR_INVALID_ARG;
+    return mm::scf_coeffs_to_image<false>(h, h->d_rtable, coeffs, precision, n, out, workspace, workspace_bytes, stream);
+}
+
+int mm_scfpyr_build_adjoint(const mm_scfpyr_t* h, void* const* grad_coeffs, int precision, int64_t n, void* grad_images,
+                            void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!h) return MM_ERR_INVALID_ARG;
+    return mm::scf_coeffs_to_image<true>(h, h->d_table, grad_coeffs, precision, n, grad_images, workspace, workspace_bytes,
+                                         stream);
+}
+
+int mm_scfpyr_reconstruct_adjoint(const mm_scfpyr_t* h, const void* grad_image, int precision, int64_t n, void* const* grad_coeffs,
+                                  void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!h) return MM_ERR_INVALID_ARG;
+    return mm::scf_image_to_coeffs<true>(h, h->d_rtable, grad_image, precision, n, grad_coeffs, workspace, workspace_bytes,
+                                         stream);
 }
 
 }  // extern "C"

@@ -77,7 +77,8 @@ class Phase_Difference_Extractor(object):
     # -- reference API -------------------------------------------------------------------
     def build_pyramid(self, im_batch, symmetry=True):
         """im_batch [B, P, W, H] -> coefficients [B, nbands, P, W_l, H_l, 2] (a list when extract_level is
-        a list) -- api/phase_difference_extractor.py:38-87."""
+        a list) -- api/phase_difference_extractor.py:38-87.  Differentiable on a general configuration (torch ops around
+        SCFpyr_PyTorch.build); the fused hot-path configuration is inference-only."""
         self._check_input(im_batch, 4, "im_batch")
         B, P, W, H = im_batch.shape
         assert W == H, "square frames only (SCFpyr_PyTorch.py:87 swaps height/width)"

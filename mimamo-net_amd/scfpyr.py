@@ -5,6 +5,11 @@ square images, and `reconstruct(coeff)` turns such a list -- edited or not -- ba
 the arithmetic runs in libmimamo_hip.so (csrc/scfpyr.hip: DFT-by-summation with float64 accumulation).  The
 inference pipeline does not use this class -- Phase_Difference_Extractor.build_pyramid calls the mirrored-input
 kernel of csrc/pyramid.hip, which produces only the coefficients the phase stage keeps.
+
+Both methods are differentiable, like the reference's torch-op pyramid: when grad mode is on and an input requires grad
+they run through the autograd Functions at the end of this file, whose backward passes are the native adjoints
+(mm_scfpyr_build_adjoint / mm_scfpyr_reconstruct_adjoint).  Both operators are linear, so each backward is the opposite
+direction's operator, and it is itself differentiable (double backward works).
 """
 import ctypes
 
@@ -63,6 +68,41 @@ class SCFpyr_PyTorch(object):
             shapes.append((n, side.value, side.value, 2) if cplx.value else (n, side.value, side.value))
         return shapes
 
+    def _image_to_coeffs(self, x, size, adjoint=False):
+        """x [N,1,size,size] or [N,size,size] -> the flat coefficient list: the build, or (adjoint) the vector-Jacobian
+        product of reconstruct, which maps an image gradient to coefficient gradients of the build's shapes."""
+        h = self._get(size)
+        n = x.shape[0]
+        L = _lib.lib()
+        outs = [torch.empty(shape, dtype=self.dtype, device=self.device) for shape in self._output_shapes(h, n)]
+        n_out = len(outs)
+        ws_bytes = L.mm_scfpyr_workspace_bytes(h, n)
+        ws = torch.empty((max(ws_bytes, 8) // 8,), dtype=torch.float64, device=self.device)
+        ptrs = (ctypes.c_void_p * n_out)(*[o.data_ptr() for o in outs])
+        x = x.contiguous()
+        name = "mm_scfpyr_reconstruct_adjoint" if adjoint else "mm_scfpyr_build"
+        with torch.cuda.device(self.device):
+            rc = getattr(L, name)(h, _lib.ptr(x), self.precision, n, ptrs, _lib.ptr(ws), ws_bytes, _lib.current_stream())
+        _lib.check(rc, name)
+        return outs
+
+    def _coeffs_to_image(self, flat, size, adjoint=False):
+        """flat coefficient list -> the image batch [N,size,size]: the reconstruct, or (adjoint) the vector-Jacobian product
+        of build, which maps coefficient gradients to the image gradient."""
+        h = self._get(size)
+        n = flat[0].shape[0]
+        out = torch.empty((n, size, size), dtype=self.dtype, device=self.device)
+        L = _lib.lib()
+        ws_bytes = L.mm_scfpyr_workspace_bytes(h, n)
+        ws = torch.empty((max(ws_bytes, 8) // 8,), dtype=torch.float64, device=self.device)
+        flat = [c.contiguous() for c in flat]
+        ptrs = (ctypes.c_void_p * len(flat))(*[c.data_ptr() for c in flat])
+        name = "mm_scfpyr_build_adjoint" if adjoint else "mm_scfpyr_reconstruct"
+        with torch.cuda.device(self.device):
+            rc = getattr(L, name)(h, ptrs, self.precision, n, _lib.ptr(out), _lib.ptr(ws), ws_bytes, _lib.current_stream())
+        _lib.check(rc, name)
+        return out
+
     def build(self, im_batch):
         """im_batch [N,1,H,W] -> [hi [N,H,W], [bands [N,h,w,2]] per level ..., lo [N,h',w']]  (SCFpyr_PyTorch.py:70-125)."""
         assert im_batch.device == self.device, 'Devices invalid (pyr = {}, batch = {})'.format(self.device, im_batch.device)
@@ -72,17 +112,10 @@ class SCFpyr_PyTorch(object):
         n, _, hh, ww = im_batch.shape
         if hh != ww:
             raise NotImplementedError("square images only (SCFpyr_PyTorch.py:87 swaps height and width)")
-        h = self._get(hh)
-        L = _lib.lib()
-        outs = [torch.empty(shape, dtype=self.dtype, device=self.device) for shape in self._output_shapes(h, n)]
-        n_out = len(outs)
-        ws_bytes = L.mm_scfpyr_workspace_bytes(h, n)
-        ws = torch.empty((max(ws_bytes, 8) // 8,), dtype=torch.float64, device=self.device)
-        ptrs = (ctypes.c_void_p * n_out)(*[o.data_ptr() for o in outs])
-        x = im_batch.contiguous()
-        with torch.cuda.device(self.device):
-            rc = L.mm_scfpyr_build(h, _lib.ptr(x), self.precision, n, ptrs, _lib.ptr(ws), ws_bytes, _lib.current_stream())
-        _lib.check(rc, "mm_scfpyr_build")
+        if torch.is_grad_enabled() and im_batch.requires_grad:
+            outs = list(_ImageToCoeffs.apply(self, hh, False, im_batch))
+        else:
+            outs = self._image_to_coeffs(im_batch, hh)
         coeff = [outs[0]]
         k = 1
         for _ in range(self.height - 2):
@@ -116,14 +149,41 @@ class SCFpyr_PyTorch(object):
         for i, (c, shape) in enumerate(zip(flat, shapes)):
             if tuple(c.shape) != shape:
                 raise ValueError("reconstruct: coefficient {} has shape {}, expected {}".format(i, tuple(c.shape), shape))
-        out = torch.empty((n, size, size), dtype=self.dtype, device=self.device)
-        L = _lib.lib()
-        ws_bytes = L.mm_scfpyr_workspace_bytes(h, n)
-        ws = torch.empty((max(ws_bytes, 8) // 8,), dtype=torch.float64, device=self.device)
-        flat = [c.contiguous() for c in flat]
-        ptrs = (ctypes.c_void_p * len(flat))(*[c.data_ptr() for c in flat])
-        with torch.cuda.device(self.device):
-            rc = L.mm_scfpyr_reconstruct(h, ptrs, self.precision, n, _lib.ptr(out), _lib.ptr(ws), ws_bytes,
-                                         _lib.current_stream())
-        _lib.check(rc, "mm_scfpyr_reconstruct")
-        return out
+        if torch.is_grad_enabled() and any(c.requires_grad for c in flat):
+            return _CoeffsToImage.apply(self, size, False, *flat)
+        return self._coeffs_to_image(flat, size)
+
+
+# The two directions as autograd Functions.  Both operators are linear, so no tensor is saved: the backward of an
+# image -> coefficients map (the build, or the reconstruct adjoint) is the coefficients -> image map with the opposite
+# `adjoint` flag, and vice versa, applied through the other Function so that the backward is itself differentiable.
+# The backward resolves the native handle by size (pyr._get): between forward and backward the same pyramid object may
+# have been used at another size, which replaces its handle.
+
+class _ImageToCoeffs(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pyr, size, adjoint, x):
+        ctx.pyr, ctx.size, ctx.adjoint, ctx.x_shape = pyr, size, adjoint, x.shape
+        return tuple(pyr._image_to_coeffs(x, size, adjoint))
+
+    @staticmethod
+    def backward(ctx, *grads):
+        if not ctx.needs_input_grad[3]:
+            return None, None, None, None
+        g = _CoeffsToImage.apply(ctx.pyr, ctx.size, not ctx.adjoint, *[t.contiguous() for t in grads])
+        return None, None, None, g.reshape(ctx.x_shape)
+
+
+class _CoeffsToImage(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pyr, size, adjoint, *flat):
+        ctx.pyr, ctx.size, ctx.adjoint = pyr, size, adjoint
+        return pyr._coeffs_to_image(flat, size, adjoint)
+
+    @staticmethod
+    def backward(ctx, grad):
+        need = ctx.needs_input_grad[3:]
+        if not any(need):
+            return (None,) * (3 + len(need))
+        gs = _ImageToCoeffs.apply(ctx.pyr, ctx.size, not ctx.adjoint, grad.contiguous())
+        return (None, None, None) + tuple(g if k else None for g, k in zip(gs, need))

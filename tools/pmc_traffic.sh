@@ -4,15 +4,18 @@
 # 16-byte-per-lane streaming reads; checked on a 1x1 conv whose operand read is known).  Writes
 # gpurun_out/r06_conv_traffic_<clips>clips.json and gpurun_out/r06_phase_traffic_<clips>clips.json, each stamped with the hash of
 # the kernel sources they were measured on (bench.py only quotes a summary whose hash matches).  usage: tools/pmc_traffic.sh [clips]
+# Every GPU step runs under its own time limit, and the first failed pass ends the script (a profiled run that faulted or
+# timed out is not followed by another one, nor summarised).
 CLIPS=${1:-32}
 STEPS=2; WARM=1
+R=$(cd "$(dirname "$0")/.." && pwd)   # the repository this script lies in
 cd /tmp && export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
 mkdir -p $R/gpurun_out
 for c in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/bt_$c
-  rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/bt_$c -o out -- \
-      python $R/bench.py --steps $STEPS --warmup $WARM --clips $CLIPS --no-cpu-baseline --no-extra > /tmp/bt_$c.log 2>&1
+  timeout -k 10 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/bt_$c -o out -- \
+      python $R/bench.py --steps $STEPS --warmup $WARM --clips $CLIPS --no-cpu-baseline --no-extra > /tmp/bt_$c.log 2>&1 \
+      || { echo "pmc_traffic: the $c pass failed (exit $?)"; tail -5 /tmp/bt_$c.log; exit 1; }
 done
 python - "$CLIPS" "$STEPS" "$WARM" "$R" <<'PY'
 import csv, glob, json, sys
