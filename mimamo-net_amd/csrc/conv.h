@@ -15,6 +15,10 @@ struct ConvParams {
     int B, H, W, Cin, in_cstride, in_coff;
     int Ho, Wo, Cout, out_cstride, out_coff;
     int res_cstride, res_coff;
+    // strided residual (1x1 layers, pad 0, single problem only; res_rs <= 1 = the residual shares the output's rows): the residual lives on its
+    // own grid [B][RH][RW] and output pixel (b, yo, xo) adds res(b, yo * res_rs, xo * res_rs) -- a stage-tail increase conv computed only at the
+    // pixels the next stage's stride-2 convs read (nets.hip); the row is split with div_hw / div_wo below
+    int res_rs, RH, RW;
     int kh, kw, stride, pad;
     int K, Kpad;
     int korder;      // 0: k=(r,s,c)   1: k=(c/16,r,s,c%16), needs Cin % 16 == 0   2: packed 3-channel rows (see conv_mfma.hip)

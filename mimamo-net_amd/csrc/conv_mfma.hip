@@ -128,7 +128,9 @@ constexpr int CLD = 16;   // LDS row = one 16-float chunk; the four 16-byte slot
 // (the scheduled 1x1 loop of the 128x128 tile would take 188 registers -- every fragment read of a step in flight at once -- where its mode-3
 //  twin's 156 keep three workgroups on a CU: held to three waves per SIMD.  The bf16x3 instantiations are held to the occupancy of their fp32 twins: the eight-wave one needs 133 registers where 128 keep two
 //  workgroups on a CU; the four-wave 128x256 one -- 64x128 wave tiles -- 280 where 256 keep two waves on a SIMD)
-template <int BM, int BN, int WGM, int WGN, int KMODE, bool ABL = false, int X3 = 0>
+// RS: the strided-residual epilogue (ConvParams::res_rs > 1) -- an instantiation of its own (KMODE 3 only), so that every other kernel is
+// compiled exactly as without it (as a run-time branch it cost them 29 VGPRs and a wave of occupancy)
+template <int BM, int BN, int WGM, int WGN, int KMODE, bool ABL = false, int X3 = 0, bool RS = false>
 __global__ void __launch_bounds__(WGM * WGN * 64)
     __attribute__((amdgpu_waves_per_eu(X3 == 2 ? 2 : X3 ? (WGM * WGN == 8 ? 4 : 2) : (KMODE >= 7 && WGM * WGN == 4 && BM * BN == 128 * 128) ? 3 : 1, 8)))
 conv_mfma_kernel(const ConvParams p) {
@@ -843,6 +845,14 @@ conv_mfma_kernel(const ConvParams p) {
     // then owns 4 consecutive channels of a row: bias/residual/output all move as 16-byte, 256-byte-per-row
     // coalesced accesses.
     const bool wide = ((p.Cout | p.out_cstride | p.out_coff | p.res_cstride | p.res_coff) & 3) == 0;
+    // row of the residual tensor that output row m adds: m itself, or (strided residual, ConvParams::res_rs) pixel (yo * rs, xo * rs) of image b
+    // on the residual's own [B][RH][RW] grid
+    auto res_row = [&](int m) -> int64_t {
+        if constexpr (!RS) return m;
+        const int b = fastdiv(m, p.div_hw_mul, p.div_hw_sh), rem = m - b * hw_out;
+        const int yo = fastdiv(rem, p.div_wo_mul, p.div_wo_sh), xo = rem - yo * p.Wo;
+        return ((int64_t)b * p.RH + yo * p.res_rs) * p.RW + xo * p.res_rs;
+    };
     if (wide) {
         constexpr int SLD = WN + 4;                 // staging row stride (floats)
         constexpr int QN = WN / 4;                  // float4 per staged row
@@ -868,7 +878,7 @@ conv_mfma_kernel(const ConvParams p) {
 #pragma unroll
                 for (int t = 0; t < 32 / RPI; ++t) {
                     const int m = m0 + t * RPI + qr;
-                    const int64_t mo = (nok && m < p.M) ? (int64_t)m * p.res_cstride + p.res_coff + n0 : 0;
+                    const int64_t mo = (nok && m < p.M) ? res_row(m) * p.res_cstride + p.res_coff + n0 : 0;
                     rsd[t] = *reinterpret_cast<const float4*>(p.res + mo);
                 }
             }
@@ -915,7 +925,7 @@ conv_mfma_kernel(const ConvParams p) {
                 const int m = m_base + wm * WM + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
                 if (nok && m < p.M) {
                     float v = acc[i][j][e] + bias;
-                    if (p.res) v += p.res[(int64_t)m * p.res_cstride + p.res_coff + n];
+                    if (p.res) v += p.res[res_row(m) * p.res_cstride + p.res_coff + n];
                     if (p.relu) v = fmaxf(v, 0.f);
                     if (p.post_scale) v = v * ps + pt;
                     out_b[(int64_t)m * p.out_cstride + p.out_coff + n] = v;
@@ -981,7 +991,7 @@ static int num_cus() {
     return v;
 }
 
-template <int BM, int BN, int WGM, int WGN, int KMODE, bool ABL = false, int X3 = 0>
+template <int BM, int BN, int WGM, int WGN, int KMODE, bool ABL = false, int X3 = 0, bool RS = false>
 static int launch_km(ConvParams p, hipStream_t stream) {
     fastdiv_make(p.Ho * p.Wo, p.div_hw_mul, p.div_hw_sh);
     fastdiv_make(p.Wo, p.div_wo_mul, p.div_wo_sh);
@@ -993,10 +1003,11 @@ static int launch_km(ConvParams p, hipStream_t stream) {
     if (blocks <= 0 || blocks > 0x7fffffff) return MM_ERR_INVALID_ARG;
     if (prof_enabled()) {
         char tag[64];
-        snprintf(tag, sizeof(tag), "M=%d K=%d N=%d k%d s%d t%dx%d b%d%s", p.M - p.m_off, p.K, p.Cout, p.kh, p.stride, BM, BN, p.batch, X3 == 2 ? " x3p x3" : X3 ? " x3" : "");
+        snprintf(tag, sizeof(tag), "M=%d K=%d N=%d k%d s%d t%dx%d b%d%s%s", p.M - p.m_off, p.K, p.Cout, p.kh, p.stride, BM, BN, p.batch, X3 == 2 ? " x3p x3" : X3 ? " x3" : "",
+                 RS ? " rs" : "");
         prof_before(0, 2.0 * (double)(p.M - p.m_off) * (double)(p.kh * p.kw * p.Cin_real) * (double)p.Cout * (double)p.batch, stream, tag);
     }
-    hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WGM, WGN, KMODE, ABL, X3>), dim3((unsigned)blocks), dim3(WGM * WGN * 64), 0, stream, p);
+    hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WGM, WGN, KMODE, ABL, X3, RS>), dim3((unsigned)blocks), dim3(WGM * WGN * 64), 0, stream, p);
     prof_after(0, stream);
     MM_LAUNCH_CHECK();
     return MM_OK;
@@ -1015,6 +1026,7 @@ static int launch_cfg(const ConvParams& p, hipStream_t stream) {
         if (p.x3 && p.in2) return launch_km<BM, BN, WGM, WGN, 6, false, 1>(p, stream);
         if (p.x3 && p.kh == 1 && p.kw == 1 && p.pad == 0) return launch_km<BM, BN, WGM, WGN, 3, false, 1>(p, stream);
     }
+    if (p.res && p.res_rs > 1) return launch_km<BM, BN, WGM, WGN, 3, false, 0, true>(p, stream);   // (conv_forward: a plain 1x1 layer)
     if (p.sched1x1 && p.in2) return launch_km<BM, BN, WGM, WGN, 8>(p, stream);
     if (p.sched1x1) return launch_km<BM, BN, WGM, WGN, 7>(p, stream);
     if (p.in2) return launch_km<BM, BN, WGM, WGN, 6>(p, stream);
@@ -1063,6 +1075,13 @@ int conv_forward(const ConvParams& p0, hipStream_t stream) {
         const int64_t hw_o = (int64_t)p.Ho * p.Wo;
         const int64_t span = 256 / (hw_o > 0 ? hw_o : 1) + 2;
         if (span * p.H2 * p.W2 * p.in2_cstride * 4 >= 0x7FFFF000ll) return MM_ERR_INVALID_ARG;
+    }
+    if (p.res && p.res_rs > 1) {   // strided residual: 1x1 layers, every output pixel's residual pixel inside the residual's grid
+        if (p.kh != 1 || p.kw != 1 || p.pad != 0 || p.korder != 0 || p.batch > 1 || p.hpool || p.in2 || p.force_tile >= 16 ||
+            (int64_t)(p.Ho - 1) * p.res_rs >= p.RH || (int64_t)(p.Wo - 1) * p.res_rs >= p.RW)
+            return MM_ERR_INVALID_ARG;
+        p.x3 = 0;          // the strided-residual epilogue exists on the fp32 1x1 loop (KMODE 3) only
+        p.no_sched = 1;
     }
     if (p.x3 && !(p.kh == 1 && p.kw == 1 && p.pad == 0 && p.korder == 0)) p.x3 = 0;   // bf16x3 exists for the 1x1 forms only
     if (p.hpool) {   // horizontally pooled output: the stem form on the 128x64 tile only (the tile is the whole channel range)
@@ -1175,6 +1194,7 @@ int conv_forward(const ConvParams& p0, hipStream_t stream) {
             // in the loop.  Measured SLOWER than the four-wave form below that splits both operands in the loop (154-181 vs 183-206 TFLOP/s per layer,
             // profiles/r06_ab_x3_presplit.txt): 96 B per B row and ring slot make the ring 96 KB -- one workgroup per CU -- and the 64x64 wave tiles
             // amortise the remaining A split over two column tiles instead of four
+            if (p.res && p.res_rs > 1) return launch_km<128, 256, 2, 4, 3, false, 0, true>(p, stream);
             if (p.x3 && p.w3) return p.in2 ? launch_km<128, 256, 2, 4, 6, false, 2>(p, stream) : launch_km<128, 256, 2, 4, 3, false, 2>(p, stream);
 #if MM_X3_WIDE
             if (p.x3) return p.in2 ? launch_km<128, 256, 2, 2, 6, false, 1>(p, stream) : launch_km<128, 256, 2, 2, 3, false, 1>(p, stream);

@@ -206,7 +206,7 @@ conv_panel_kernel(const ConvParams p) {
 }
 
 bool conv_panel_supported(const ConvParams& p) {
-    return p.kh == 1 && p.kw == 1 && p.pad == 0 && p.stride == 1 && p.korder == 0 && !p.in2 && !p.x3 && !p.post_scale && !p.hpool && p.batch <= 1 &&
+    return p.kh == 1 && p.kw == 1 && p.pad == 0 && p.stride == 1 && p.korder == 0 && !p.in2 && !p.x3 && p.res_rs <= 1 && !p.post_scale && !p.hpool && p.batch <= 1 &&
            p.H == p.Ho && p.W == p.Wo && p.K == p.Kpad && (p.K == 256 || p.K == 128) && p.Cin == p.K && p.in_cstride >= p.K && p.Cout % 256 == 0 &&
            p.Cout >= 512 && ((p.in_cstride | p.in_coff | p.out_cstride | p.out_coff | p.res_cstride | p.res_coff) & 3) == 0 &&
            (int64_t)128 * p.in_cstride * 4 < 0x7FFFF000ll;

@@ -185,16 +185,21 @@ constexpr int kX3MinK = 512;   // mm_resnet50_set_precision(h, 1): 1x1 layers wi
 
 static int run_layer(const Layer& L, const float* in, int B, int H, int W, int in_cstride, int in_coff, float* out,
                      int out_cstride, int out_coff, const float* res, int res_cstride, hipStream_t s, int* Ho_ = nullptr,
-                     int* Wo_ = nullptr, int x3 = 0, int no_sched = 0, int hpool = 0, int use_panel = 0) {
+                     int* Wo_ = nullptr, int x3 = 0, int no_sched = 0, int hpool = 0, int use_panel = 0, int stride_ov = 0, int res_rs = 0,
+                     int RH = 0, int RW = 0) {
+    // stride_ov (1x1 layers, > 0): run the layer at this stride instead of its own (stage tails and the blocks that read them, see
+    // mm_resnet50_forward); res_rs / RH / RW: strided residual (ConvParams::res_rs)
+    const int stride = stride_ov > 0 && L.k == 1 ? stride_ov : L.stride;
     ConvParams p;
     std::memset(&p, 0, sizeof(p));
     p.in = in; p.w = L.w; p.bias = L.bias; p.res = res; p.post_scale = L.ps; p.post_shift = L.pt; p.out = out;
     p.B = B; p.H = H; p.W = W; p.Cin = L.cin_p; p.in_cstride = in_cstride; p.in_coff = in_coff;
-    p.Ho = (H + 2 * L.pad - L.k) / L.stride + 1;
-    p.Wo = (W + 2 * L.pad - L.k) / L.stride + 1;
+    p.Ho = (H + 2 * L.pad - L.k) / stride + 1;
+    p.Wo = (W + 2 * L.pad - L.k) / stride + 1;
     p.Cout = L.cout; p.out_cstride = out_cstride; p.out_coff = out_coff;
     p.res_cstride = res_cstride; p.res_coff = 0;
-    p.kh = L.k; p.kw = L.k; p.stride = L.stride; p.pad = L.pad;
+    p.res_rs = res_rs; p.RH = RH; p.RW = RW;
+    p.kh = L.k; p.kw = L.k; p.stride = stride; p.pad = L.pad;
     p.K = L.K; p.Kpad = L.Kpad; p.relu = L.relu; p.Cin_real = L.cin; p.korder = L.korder; p.force_tile = L.tile;
     p.x3 = x3 && L.k == 1 && L.Kpad >= kX3MinK;
     p.w3 = p.x3 ? L.w3 : nullptr; p.w3_plane = (int64_t)L.cout * L.Kpad;
@@ -330,6 +335,15 @@ struct mm_resnet50 {
     int inc_shape; // workgroup variant of the conv2_x fused kernel (measurement knob MM_INC1_SHAPE: 8 = eight waves without NEXT)
     int fuse_inc;  // 3x3 + increase conv (+ residual | + projection) in ONE kernel (wino_fused.hip INC): 0 = never (the parity twin), 1 = conv2_x
                    // blocks 2-3, 2 = also conv2_x block 1 (increase | projection over two K sources), 3 (default) = also conv3_x blocks 2-4
+    int stage_tail;// the last block of a stage whose successor reads it through stride-2 1x1 convs only (conv2_x .. conv4_x in the stride-on-first-1x1
+                   // graph) computes its increase conv at pixels (2i, 2j) alone -- wherever that conv is a launch of its own: conv4_x in the default
+                   // schedule, every tail with MM_FUSE_INC=0 or a non-fused Winograd mode -- and hands on a compact [B][ceil(H/2)][ceil(W/2)][C]
+                   // tensor, which the next block's reduce / projection read at stride 1.  1 (default) = on; MM_STAGE_TAIL=0: full-size tails
+                   // (the parity twin: every kept element is the same sum in the same order, bit-identical)
+    int tail_fused;// the fused 3x3 + increase kernels write full-size output.  MM_STAGE_TAIL_FUSED bits: 1 = conv2_x's tail, 2 = conv3_x's tail stays in
+                   // the fused kernel (default 3: both).  A cleared bit runs that tail as the plain fused 3x3 and an increase launch of its own,
+                   // which MM_STAGE_TAIL then compacts -- opt-in: measured 2.9 ms per step faster with both cleared (profiles/stage_tail_ab.txt),
+                   // but two more launches and another summation order in the increase contraction than the fused form (not bit-equal to it)
     int device;
 };
 
@@ -468,6 +482,10 @@ int mm_resnet50_create(mm_resnet50_t** out, const float* blob, int64_t n_floats,
         h->fuse_next = fn ? atoi(fn) : 0;
         const char* is = getenv("MM_INC1_SHAPE");  // measurement knob: 8 = the conv2_x fused kernel as eight-wave workgroups (without NEXT)
         h->inc_shape = is ? atoi(is) : 0;
+        const char* tl = getenv("MM_STAGE_TAIL");  // parity twin: 0 = stage-tail blocks at full size (same kernels)
+        h->stage_tail = tl ? atoi(tl) != 0 : 1;
+        const char* tf = getenv("MM_STAGE_TAIL_FUSED");  // measurement knob: bit 0 = conv2_x's, bit 1 = conv3_x's tail stays in the fused 3x3 + increase kernel
+        h->tail_fused = tf ? atoi(tf) & 3 : 3;
     }
     auto conv_bn = [&](Layer& L, int cout, int cin, int k, int stride, int pad, int relu) {
         const float* w = p;
@@ -651,6 +669,8 @@ int mm_resnet50_forward(mm_resnet50_t* h, const float* images, int nchw, int64_t
     int C = 64;
     const int x3 = h->precision == 1, ns = h->no_sched;
     bool reduce_done = false;   // the previous block's fused kernel has already written this block's reduce output into y1 (fuse_next)
+    bool xc = false;            // the block input is a compact stage tail: [B][H][W][C] holds pixels (2i, 2j) of the previous stage's output,
+                                // and the stride-2 1x1 convs that read it run at stride 1
     for (size_t bi = 0; bi < h->blocks.size(); ++bi) {
         const Bottleneck& Bk = h->blocks[bi];
         const Bottleneck* Nx = bi + 1 < h->blocks.size() ? &h->blocks[bi + 1] : nullptr;
@@ -660,8 +680,18 @@ int mm_resnet50_forward(mm_resnet50_t* h, const float* images, int nchw, int64_t
         int H1, W1, H2, W2, H3, W3;
         const float* resid = x;
         const bool dual = Bk.has_proj && h->fuse_proj && Bk.inc_proj.w;
+        // stage tail: every reader of this block's output is a 1x1 / stride 2 / pad 0 conv of the next block (its reduce and its projection
+        // shortcut), so only pixels (2i, 2j) are ever read.  (A tail that is itself the first block of a stage does not occur in kStages.)
+        const bool tail_blk = !Bk.has_proj && Nx && Nx->has_proj && Nx->proj_stride == 2 && Nx->reduce.k == 1 && Nx->reduce.stride == 2 &&
+                              Nx->reduce.pad == 0 && Nx->proj.k == 1 && Nx->proj.pad == 0 && Bk.increase.k == 1 && Bk.increase.stride == 1 &&
+                              Bk.increase.pad == 0;
+        bool tail = tail_blk && h->stage_tail && !h->use_panel;   // (the opt-in panel kernel has no strided form: under MM_CONV_PANEL tails stay full-size)
+        // the fused 3x3 + increase kernels write full-size output: on request (tail_fused) a stage tail leaves them for the plain fused 3x3 and an
+        // increase launch of its own, compact or (the twin) not
+        const bool tail_unfuse = tail_blk && !(h->tail_fused & (Bk.conv3.cout == 64 ? 1 : 2));
+        const int sov = xc ? 1 : 0;     // stride of this block's reduce / projection on a compact input
         if (Bk.has_proj && !dual) {
-            rc = run_layer(Bk.proj, x, B, H, W, C, 0, sc, Bk.proj.cout, 0, nullptr, 0, s, nullptr, nullptr, x3, ns);
+            rc = run_layer(Bk.proj, x, B, H, W, C, 0, sc, Bk.proj.cout, 0, nullptr, 0, s, nullptr, nullptr, x3, ns, 0, 0, sov);
             if (rc != MM_OK) return rc;
             resid = sc;
         }
@@ -669,7 +699,7 @@ int mm_resnet50_forward(mm_resnet50_t* h, const float* images, int nchw, int64_t
             H1 = H; W1 = W;                        // y1 was written by the pool kernel / by the previous block's fused kernel
             reduce_done = false;
         } else {
-            rc = run_layer(Bk.reduce, x, B, H, W, C, 0, y1, Bk.reduce.cout, 0, nullptr, 0, s, &H1, &W1, x3, ns);
+            rc = run_layer(Bk.reduce, x, B, H, W, C, 0, y1, Bk.reduce.cout, 0, nullptr, 0, s, &H1, &W1, x3, ns, 0, 0, sov);
             if (rc != MM_OK) return rc;
         }
         // default (1): conv2_x..conv4_x (Cin <= 256) take the fused kernel, conv5_x the three-kernel form (Cin = 512: its
@@ -680,7 +710,7 @@ int mm_resnet50_forward(mm_resnet50_t* h, const float* images, int nchw, int64_t
         if (wm_ && Bk.conv3.wino_u &&
             (int64_t)(wt_ + 2) * (wt_ + 2) * ((H1 + wt_ - 1) / wt_) * ((W1 + wt_ - 1) / wt_) * Bk.conv3.cin <= kRsWino) {
             rc = MM_ERR_UNSUPPORTED;
-            if (wm_ == 5 && h->fuse_inc && !Bk.has_proj && (Bk.conv3.cout == 64 || h->fuse_inc >= 3)) {
+            if (wm_ == 5 && h->fuse_inc && !Bk.has_proj && !tail_unfuse && (Bk.conv3.cout == 64 || h->fuse_inc >= 3)) {
                 // conv2_x blocks 2, 3 (Cin = Cout = 64 -> 256) and, with MM_FUSE_INC >= 3, conv3_x blocks 2-4 (128 -> 512): 3x3 +
                 // increase + residual + ReLU in one kernel
                 // ... and (fuse_next) the NEXT block's stride-1 256 -> 64 reduce conv on the block output, written to y1 -- dead once the input transform
@@ -708,15 +738,22 @@ int mm_resnet50_forward(mm_resnet50_t* h, const float* images, int nchw, int64_t
         if (rc != MM_OK) return rc;
         if (inc_done) {
             H3 = H2; W3 = W2;
+            tail = false;               // (the fused kernel wrote the full-size output)
         } else if (dual) {
             // relu(BN(increase(y2)) + BN(proj(x))) in one accumulation: the shortcut tensor is never written or re-read
-            rc = run_layer_dual(Bk.inc_proj, y2, B, H2, W2, x, H, W, C, Bk.proj_stride, o, s, x3, ns);
+            rc = run_layer_dual(Bk.inc_proj, y2, B, H2, W2, x, H, W, C, xc ? 1 : Bk.proj_stride, o, s, x3, ns);
             H3 = H2; W3 = W2;
+        } else if (tail) {
+            // the increase conv at stride 2 over y2, the residual x read at the same pixels, compact output (each kept element is the same sum
+            // in the same order as in the full-size launch)
+            rc = run_layer(Bk.increase, y2, B, H2, W2, Bk.conv3.cout, 0, o, Bk.increase.cout, 0, resid, Bk.increase.cout, s, &H3, &W3, x3, ns, 0,
+                           h->use_panel, 2, 2, H2, W2);
         } else {
             rc = run_layer(Bk.increase, y2, B, H2, W2, Bk.conv3.cout, 0, o, Bk.increase.cout, 0, resid, Bk.increase.cout, s, &H3, &W3, x3, ns, 0, h->use_panel);
         }
         if (rc != MM_OK) return rc;
         H = H3; W = W3; C = Bk.increase.cout;
+        xc = tail;
         xi = (xi + 2) % 3;
     }
     // pool5_7x7_s1 + relu(squeeze)  (resnet50_extractor.py:83)
